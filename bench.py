@@ -18,12 +18,17 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
                  `sq_counters` from a third pass (SQ_VALU_MFMA_BUSY_CYCLES, wave-cycle split; counters for the GEMM kernels only);
                  `by_class` = every Linear class against its own bound (MFMA or HBM) with its tile-quantisation ceiling.
   value        - the bf16 leg (BASELINE.json config 2's dtype); f16_value = the same runner on IEEE f16 operands;
-                 parity_qualified_value = the f16x3 leg (every kept set identical to the oracle).  The timed region repeats the K
-                 steps in whole passes until it lasts >= 1 s (timed_passes_of_k_steps); ms_per_step is per step.
+                 parity_qualified_value = the f16x3 leg (every kept set identical to the oracle).  The timed region is exactly
+                 the K = --steps forwards after the warm-up; ms_per_step = its wall time / K.
   parity_mode  - the same workload timed in the precision mode that carries the parity claim ("f16x3": fp32-accurate GEMMs
                  on the f16 MFMA) + index_match of every mode vs the CPU oracle at the headline batch.
   cpu_baseline - oracle/ (the CPU restatement of the reference forward, kind "port") timed on this box's host cores on a
                  bounded sample of the same workload (rank 0, N=1 only).
+
+--dump-outputs DIR writes what the timed path returned for its last step (rank 0: the forward on the seeded headline inputs,
+worker 0 of the in-flight runner) as DIR/<name>.npy in float32 / float64, at most 64 MiB in all (a larger output is replaced by a
+fixed, seeded sample of its flattened elements).  Weights and inputs are seeded, so two builds run with the same arguments can be
+compared output for output.
 """
 import argparse
 import json
@@ -192,26 +197,21 @@ def measure_traffic(args):
                    "--config", args.config, "--precision", args.precision, "--steps", "1", "--warmup", "1", "--traffic", "off", "--min-seconds", "0",
                    "--no-cpu-baseline", "--no-parity", "--no-bf16-leg", "--no-gemm-events", "--inflight", "1"] + (["--batch", str(args.batch)] if args.batch else [])
             env = dict(os.environ, TMPDIR="/tmp")
-            # A profiled child occasionally hangs (seen about once in ten calls on the pool's boxes, also as the first GPU user of a
-            # call): every pass gets a bounded time and ONE retry, the three passes together at most MADTP_TRAFFIC_BUDGET seconds
-            # (a pass normally takes 12-15 s), so that a hang costs the line its counters at worst, never the run its minutes.
-            r, dbs = None, []
-            for attempt in range(2):
-                left = deadline - time.time()
-                if left < 20:
-                    break
-                shutil.rmtree(d, ignore_errors=True)
-                r = run_bounded(cmd, "/tmp", env, min(left, float(os.environ.get("MADTP_TRAFFIC_TIMEOUT", "75"))))
-                if r is None:
-                    print(f"[bench] traffic pass {counter}: attempt {attempt + 1} timed out", file=sys.stderr)
-                    continue
-                dbs = [os.path.join(dp, f) for dp, _, fs in os.walk(d) for f in fs if f.endswith("_results.db")]
-                if r.returncode == 0 and dbs:
-                    break
-            if r is None:
+            # Every pass gets a bounded time, the three passes together at most MADTP_TRAFFIC_BUDGET seconds (a pass normally takes
+            # 12-15 s).  A pass is never started again: a profiled child that hung or died of a signal (GPU fault, abort,
+            # segmentation fault) ends this run before it touches the GPU itself.
+            left = deadline - time.time()
+            if left < 20:
+                print(f"[bench] traffic pass {counter}: skipped, budget spent", file=sys.stderr)
                 if counter == "SQ":
                     break
                 return None
+            r = run_bounded(cmd, "/tmp", env, min(left, float(os.environ.get("MADTP_TRAFFIC_TIMEOUT", "75"))))
+            if r is None or r.returncode < 0 or r.returncode in (134, 139):
+                what = "timed out" if r is None else f"died with status {r.returncode}; stderr tail: {r.stderr[-600:]}"
+                raise SystemExit(f"[bench] traffic pass {counter} {what}: no further GPU work in this run "
+                                 "(--traffic off skips the counter passes)")
+            dbs = [os.path.join(dp, f) for dp, _, fs in os.walk(d) for f in fs if f.endswith("_results.db")]
             if r.returncode != 0 or not dbs:
                 print(f"[bench] traffic pass {counter}: rc {r.returncode}, {len(dbs)} result files; stderr tail: {r.stderr[-600:]}", file=sys.stderr)
                 if counter == "SQ":
@@ -270,9 +270,11 @@ def main():
     ap.add_argument("--no-gemm-events", action="store_true")
     ap.add_argument("--no-bf16-leg", action="store_true", help="skip the timed leg in the OTHER fast mode (f16_value of a bf16 run, bf16_value of an f16 run)")
     ap.add_argument("--bf16-steps", type=int, default=32, help="timed steps of that leg")
-    ap.add_argument("--min-seconds", type=float, default=1.0,
-                    help="the timed region repeats the K steps (whole passes of K) until it lasts at least this long; ms_per_step is per step "
-                         "(the driver's --steps 20 is 0.1 s of work: ramp-up and tail of the in-flight pipeline were ~5 %% of it)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="0 (default): the timed region is exactly the K = --steps forwards.  > 0: it repeats the K steps (whole passes "
+                         "of K) until it lasts at least this long; ms_per_step is per step either way")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step (rank 0) as DIR/<name>.npy, float32 / float64, <= 64 MiB in all")
     ap.add_argument("--partition", default=None,
                     help="CUs per XCD of the in-flight workers, e.g. 8,8,8,8 (CU-masked streams, madtp_amd/pipeline.py); 'off' = priority "
                          "streams on the whole chip; default: MADTP_INFLIGHT_CUMASK, else the workload's measured default")
@@ -353,12 +355,15 @@ def main():
                                 models=model if share else [model] + [w.build("cuda") for _ in range(n_slots - 1)])
         runner.inputs[0] = inp
 
+    last = [None]  # what the most recent run_steps() returned for the headline inputs `inp`
+
     def run_steps(n):  # n whole forwards: serial on the current stream, or spread over the in-flight workers
         if runner is not None:
             runner.run(n, workers=args.inflight)
+            last[0] = runner.last[0]  # worker 0 runs on `inp`
         else:
             for _ in range(n):
-                step()
+                last[0] = step()
 
     single = None
     with torch.no_grad():
@@ -375,12 +380,14 @@ def main():
             torch.cuda.synchronize()
             single = time.perf_counter() - ts
         torch.cuda.synchronize()
-        # how many passes of K steps make the timed region >= --min-seconds: from one untimed pass, the same count on every rank
-        tp = time.perf_counter()
-        run_steps(args.steps)
-        torch.cuda.synchronize()
-        est = mdist.max_over_ranks(time.perf_counter() - tp, device=red_dev)
-        repeats = max(1, min(200, int(-(-args.min_seconds // max(est, 1e-4)))))
+        repeats = 1
+        if args.min_seconds > 0:
+            # how many passes of K steps make the timed region >= --min-seconds: from one untimed pass, the same count on every rank
+            tp = time.perf_counter()
+            run_steps(args.steps)
+            torch.cuda.synchronize()
+            est = mdist.max_over_ranks(time.perf_counter() - tp, device=red_dev)
+            repeats = max(1, min(200, int(-(-args.min_seconds // max(est, 1e-4)))))
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
@@ -393,6 +400,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        # host copies before anything else runs: an output may live in a workspace that the next forward reuses
+        dumped = (dump_arrays(args.config, last[0]) if args.dump_outputs and rank == 0 else None)
+        last[0] = None
         hl_high = runner.n_high if runner is not None else 0  # high-priority streams among the workers the headline leg used
         hl_part = runner.last_partition if runner is not None else None  # CUs per XCD of its workers (CU-masked streams), or None
         weight_bytes = sum(p.numel() * p.element_size() for p in model.parameters())
@@ -457,7 +467,7 @@ def main():
     out = {
         "metric": METRIC if headline else f"images/sec forward, {args.config} configuration of BASELINE.json (p={w.p})",
         "value": round(value, 1), "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(1e3 * elapsed / args.steps, 3), "timed_passes_of_k_steps": repeats,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 3), "timed_steps": args.steps * repeats, "timed_passes_of_k_steps": repeats,
         "timed_seconds": round(elapsed * repeats, 3), "higher_is_better": True, "scaling": "strong" if strong else "weak",
         "vs_baseline": None, "dtype": {"bf16": "bf16", "f16": "f16", "fp32": "f32", "f16x3": "f16x3 (fp32-accurate)"}[args.precision],
         "data": "synthetic",
@@ -562,6 +572,8 @@ def main():
             out["parity_mode"]["index_match_batch"] = im["batch"]
         if not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.config, w, T)
+    if dumped is not None:
+        out["dump_outputs"] = write_dump(args.dump_outputs, dumped)
     if rank == 0 and args.gemm_breakdown and not args.no_gemm_events:
         print(gemm_breakdown(prof_rows, args.steps), file=sys.stderr, flush=True)
     if rank == 0:
@@ -569,6 +581,54 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+# names of what Workload.step() returns, in order (madtp_amd/workloads.py)
+OUTPUT_NAMES = {"nlvr": ["logits"], "retrieval": ["itm_logits", "itc_similarity"], "clip": ["similarity"], "vqa": ["question_states"]}
+DUMP_LIMIT_BYTES = 60_000_000  # of array data: under 64 MB with the .npy headers
+
+
+def dump_arrays(config, result):
+    """the tensors of one step's result, on the host: [(name, tensor)]"""
+    ts = [t.detach().cpu() for t in _leaves(result)]
+    names = OUTPUT_NAMES.get(config, [])
+    if len(names) != len(ts):
+        names = [f"out{i}" for i in range(len(ts))]
+    return list(zip(names, ts))
+
+
+def write_dump(d, arrays):
+    """DIR/<name>.npy in float64 (float64 and integer outputs) or float32 (every other dtype).  Arrays are written whole while they
+    fit an equal share of what is left of DUMP_LIMIT_BYTES (smallest first); a larger one is replaced by a seeded sample of that
+    many of its flattened elements, in index order (the same elements on every run)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    wide = lambda t: t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)  # noqa: E731
+    arrays = [(n, t.to(torch.float64 if wide(t) else torch.float32)) for n, t in arrays]
+    rep = {"dir": d, "sampled": False, "arrays": {}}
+    left = DUMP_LIMIT_BYTES
+    order = sorted(range(len(arrays)), key=lambda i: arrays[i][1].numel() * arrays[i][1].element_size())
+    for j, i in enumerate(order):
+        n, t = arrays[i]
+        k = min(t.numel(), (left // (len(order) - j)) // t.element_size())
+        a = t.reshape(-1) if k < t.numel() else t
+        if k < t.numel():
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            a, rep["sampled"] = a[idx], True
+        left -= a.numel() * a.element_size()
+        np.save(os.path.join(d, f"{n}.npy"), a.numpy())
+        rep["arrays"][n] = {"shape": list(t.shape), "dtype": str(a.dtype).replace("torch.", ""), "saved_elements": a.numel()}
+    return rep
+
+
+def _leaves(o):
+    if torch.is_tensor(o):
+        return [o]
+    if isinstance(o, dict):
+        return [t for k in sorted(o) for t in _leaves(o[k])]
+    if isinstance(o, (list, tuple)):
+        return [t for x in o for t in _leaves(x)]
+    return []
 
 
 def dry_run(args, world, rank):

@@ -4,7 +4,8 @@
     reference model's (recorded in the golden fixtures by tools/make_golden.py);
   * load_checkpoint semantics (models/blip.py:254-278, models/blip_nlvr.py:130-159): position-embedding interpolation equals
     the reference's, twin-branch key duplication, shape filtering.
-The reference-importing tests are skipped where /root/reference is absent (the GPU box); the checkpoint tests run anywhere."""
+The reference-importing tests are skipped where the reference tree is absent; the checkpoint tests and the stand-in / fixture
+versions of the import-order and pos-embed checks run anywhere."""
 import os
 import subprocess
 import sys
@@ -191,6 +192,42 @@ def test_interpolate_pos_embed_equals_reference():
         print("ok")
         """)
     assert "ok" in out
+
+
+def test_install_after_foreign_models_import_is_refused(tmp_path):
+    """The refusal above without the reference tree: a stand-in `models` package whose vit.py is not a mirror."""
+    (tmp_path / "models").mkdir()
+    (tmp_path / "models" / "__init__.py").write_text("")
+    (tmp_path / "models" / "vit.py").write_text("FOREIGN = True\n")
+    _run(f"""
+        import sys
+        sys.path.insert(0, {str(tmp_path)!r})
+        import models.vit
+        assert models.vit.FOREIGN
+        import madtp_amd.dropin as dropin
+        try:
+            dropin.install({str(tmp_path)!r})
+        except RuntimeError as e:
+            assert "before the first" in str(e)
+        else:
+            raise SystemExit("install() after `import models.vit` must be refused")
+        """)
+
+
+def test_interpolate_pos_embed_equals_reference_fixture(golden_dir):
+    """The comparison above without the reference tree: the reference's own output for a seeded 14x14 (+ CLS) grid resized to
+    24x24, recorded by tools/make_golden.py (pos_embed_384)."""
+    from madtp_amd.vit import interpolate_pos_embed
+    g = np.load(os.path.join(golden_dir, "pos_embed_384.npz"))
+    ck, ref = torch.from_numpy(g["checkpoint"]), torch.from_numpy(g["resized"])
+
+    class Enc:
+        class patch_embed: num_patches = 576
+        pos_embed = torch.zeros(1, 577, ck.shape[-1])
+    out = interpolate_pos_embed(ck, Enc)
+    assert out.shape == ref.shape == (1, 577, ck.shape[-1]) and torch.equal(out, ref)
+    Enc.patch_embed.num_patches, Enc.pos_embed = 196, torch.zeros(1, 197, ck.shape[-1])
+    assert interpolate_pos_embed(ck, Enc) is ck
 
 
 def test_load_checkpoint_semantics(tmp_path):

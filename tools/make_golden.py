@@ -1178,7 +1178,23 @@ def med_layer_options_case(name, B, L, Nimg, temperature, seed=0, pad_tail=0, Lp
           f"keys {sorted(k for k in rec if k.endswith('_idx') or k.endswith('_sort'))}")
 
 
+def pos_embed_case(name, width=64, seed=0):
+    """models/vit.py:398-422 interpolate_pos_embed: a 14x14 checkpoint grid (+ CLS) resized to this encoder's 24x24 grid (384^2
+    images); `width` channels of the 768 (the resize is per channel)."""
+    import models.vit as ref_vit
+
+    class Enc:  # the two attributes the function reads
+        class patch_embed:
+            num_patches = 576
+        pos_embed = torch.zeros(1, 577, width)
+    g = torch.Generator().manual_seed(seed)
+    ck = torch.randn(1, 197, width, generator=g)
+    out = ref_vit.interpolate_pos_embed(ck, Enc)
+    np.savez_compressed(os.path.join(GOLD, name + ".npz"), checkpoint=ck.numpy(), resized=out.numpy())
+
+
 CASES = {
+    "pos_embed_384": lambda: pos_embed_case("pos_embed_384"),
     "medopts_b2": lambda: med_layer_options_case("medopts_b2", 2, 35, 10, 30.0, pad_tail=1, Lp=20),
     "cap_gen_b2_T6": lambda: cap_gen_case("cap_gen_b2_T6", 2, 224, 6.0, 0.0, 12, 5),
     "cap_gen_b3_T30_eos": lambda: cap_gen_case("cap_gen_b3_T30_eos", 3, 224, 30.0, 2.4, 12, 5, seed=1),
