@@ -332,12 +332,16 @@ def dropout(x, p, seed, site, residual=None, per_sample=0):
     return y
 
 
-def attention_train(q, k, v, B, H, Nq, Nk, scale, drop, key_mask=None, mask_qk=None, scores=False):
+def attention_train(q, k, v, B, H, Nq, Nk, scale, drop, key_mask=None, mask_qk=None, scores=False, P=None):
     """madtp_attention_train: the training forward's attention with attention_probs dropout drop = (p, seed, site) -> (out [B*Nq, H*64],
-    side or None) like hip.attention (exact f32; P is scratch)."""
+    side or None) like hip.attention (exact f32).  P: the caller's f32 [B*H*Nq*Nk] buffer that receives the undropped probabilities,
+    or None (scratch)."""
     p, seed, site = drop
     out = torch.empty((B * Nq, H * 64), device=q.device, dtype=torch.float32)
-    P = torch.empty((B * H * Nq * Nk,), device=q.device, dtype=torch.float32)
+    if P is None:
+        P = torch.empty((B * H * Nq * Nk,), device=q.device, dtype=torch.float32)
+    elif P.dtype != torch.float32 or not P.is_contiguous() or P.numel() != B * H * Nq * Nk or P.device != q.device:
+        raise RuntimeError("attention_train: P must be a contiguous f32 buffer of B*H*Nq*Nk elements on q's device")
     cs = p0 = on = None
     if scores:
         cs = torch.empty((B, (Nq + 15) // 16, Nk), device=q.device, dtype=torch.float32)
