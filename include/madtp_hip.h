@@ -701,6 +701,40 @@ int madtp_attention_bwd(const float* q, const float* k, const float* v, int ld, 
                         int B, int H, int N, float scale, float p_drop, unsigned long long seed,
                         unsigned long long site, void* stream);
 
+/* ---- Retrieval training step (ABI 30): models/blip_retrieval.py:99-322 ---------------------------------------------------------
+ * madtp_itc_loss: one direction of the image-text contrastive loss (:116-150) and its gradient, without the [B, B+Q] matrices.
+ * Query rows q (student features) and q_m (momentum features) f32 [B,D] against the N = B + Q key columns
+ *   [keys_batch^T | queue]:  keys_batch f32 [B,D] (the other modality's in-batch momentum features - the cat(feat.T, queue)
+ *   copy of :133/:138 is never formed), queue f32 [D,Q] (the image_queue / text_queue buffer, row stride Q).
+ * Column ids: idx int64 [B] then idx_queue int64 [Q]; a column is positive for row b when its id equals idx[b].
+ * temp: device pointer to the temperature (no host read).  With s = q k / temp, s_m = q_m k / temp and
+ *   t = alpha softmax(s_m) + (1 - alpha) pos / n_pos  (the targets carry no gradient, as under the reference's no_grad):
+ *   loss[b] = -sum_j t_j log softmax(s)_j,  dq = d mean_b(loss) / dq  [B,D],  dtemp = d mean_b(loss) / d temp  [1].
+ * The gradient is formed here, before the caller overwrites the queue.  Fixed-order reductions, no atomics: bit-identical
+ * across identical calls.  ws: device workspace of madtp_itc_workspace(B, D, Q) bytes.
+ * D % 64 == 0, D <= 512, 1 <= B <= 256, Q >= 0 (queue / idx_queue may be NULL when Q == 0). */
+size_t madtp_itc_workspace(int B, int D, int Q);
+int madtp_itc_loss(const float* q, const float* q_m, const float* keys_batch, const float* queue, const int64_t* idx,
+                   const int64_t* idx_queue, const float* temp, float alpha, float* loss, float* dq, float* dtemp, void* ws,
+                   size_t ws_bytes, int B, int D, int Q, void* stream);
+/* madtp_ema_update: the momentum update of :296-300 over all pairs in one launch, in place:
+ *   p_m = p_m * m + p * one_minus_m   with the three f32 roundings of the torch expression (no contraction).
+ * table: device int64 [4, n_tensors]: row 0 the momentum f32 pointers, row 1 the source f32 pointers, row 2 the element
+ * counts, row 3 the first workgroup of each tensor (prefix sum of madtp_ema_blocks(numel)); n_blocks = the total. */
+int madtp_ema_blocks(int64_t numel);
+int madtp_ema_update(const int64_t* table, int n_tensors, int n_blocks, float m, float one_minus_m, void* stream);
+/* madtp_itm_negatives: the hard-negative draw of ITM (:220-258) for both directions in one launch.  For each row b:
+ *   direction 0 (a negative image per text): weights = softmax(text_feat[b] . image_feat_world^T / temp) over the Bw columns,
+ *   direction 1 (a negative text per image): weights = softmax(image_feat[b] . text_feat_world^T / temp),
+ * columns with idx_world == idx[b] set to 0, then the inverse CDF: neg[dir, b] = the first j with cumsum_j > u[dir, b] * sum(w).
+ * u: f32 [2,B] uniforms in [0,1) (the layout of madtp_sample_top_p's u, one row per direction); neg: int64 [2,B].
+ * A row whose weights are all 0 (every column shares its id - where torch.multinomial raises) gets neg = -1 and sets the
+ * caller's device int *flag to 1; the flag is sticky until the caller clears it.
+ * Features f32 [B,D] / [Bw,D], D % 64 == 0, D <= 512, B <= Bw <= 8192. */
+int madtp_itm_negatives(const float* image_feat, const float* text_feat, const float* image_feat_world, const float* text_feat_world,
+                        const int64_t* idx, const int64_t* idx_world, const float* temp, const float* u, int64_t* neg, int* flag,
+                        int B, int Bw, int D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,13 +1,16 @@
-"""Mirror of the reference's retrieval evaluation path:
-models/blip_retrieval.py BLIP_Retrieval (:19-66, the modules evaluation uses) and compress_retrieval_dtp.py evaluate()
-(:84-207) - text features, image features with the cross-batch CLS-repeat padding, similarity matrix, ITM re-ranking of
-the top k_test candidates in both directions with the multimodal MED encoder.
+"""Mirror of the reference's models/blip_retrieval.py BLIP_Retrieval and of compress_retrieval_dtp.py evaluate() (:84-207).
 
-Same names, constructor arguments, state-dict keys and call signatures.  The momentum encoders / queues / `temp` of the
-training loss (:67-93) are not built (their checkpoint keys are ignored by load_state_dict(strict=False)); forward()
-- the training loss - raises.  Everything heavy runs through the HIP library (pruned ViT, MED BERT in text and
-multimodal mode, projections, ITM head); torch only does the glue the reference does in torch as well (topk, row
-gathers, normalisation of [n,256] features) - on the GPU, the image tokens never visit the host."""
+evaluate=True (the reference driver's evaluation model, compress_retrieval_dtp.py:350-373) builds the modules evaluation uses
+(:19-66) - text features, image features with the cross-batch CLS-repeat padding, similarity matrix, ITM re-ranking of the top
+k_test candidates in both directions - and forward() raises.  evaluate=False (the driver's training model) adds the training
+state of :67-93 under the reference's names (visual_encoder_m, vision_proj_m, text_encoder_m, text_proj_m, image_queue,
+text_queue, idx_queue, ptr_queue, temp), so reference checkpoints load by key, and forward() is the ITC / ITM training step
+of :99-282 (see BLIP_Retrieval.forward).
+
+Everything heavy runs through the HIP library (pruned ViT, MED BERT in text and multimodal mode, projections, ITM head, and
+for training the contrastive loss over the queues, the EMA of the momentum encoders and the hard-negative draw of
+csrc/retrieval.hip); torch only does the glue the reference does in torch as well (topk, row gathers, normalisation of
+[n,256] features, the queue writes) - on the GPU, the image tokens never visit the host."""
 import os
 
 import torch
@@ -20,6 +23,60 @@ from .blip_nlvr import ENC_TOKEN_ID, create_vit
 from .bert import EncoderKVCache
 from .med import BertModel
 from .runtime import PreparedCache, compute_dtype, lin_of, require_gpu, to_compute
+
+
+def _dist_world():
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_world_size()
+    return 1
+
+
+def _all_gather(t):
+    """concat_all_gather of blip_retrieval.py:335-345 (no gradient); identity at world 1.  gloo gathers through the host."""
+    import torch.distributed as dist
+    if _dist_world() == 1:
+        return t
+    src = t if dist.get_backend() == "nccl" else t.cpu()
+    parts = [torch.empty_like(src) for _ in range(dist.get_world_size())]
+    dist.all_gather(parts, src.contiguous())
+    return torch.cat(parts, 0).to(t.device)
+
+
+class _GatherWithGrad(torch.autograd.Function):
+    """all_gather_with_grad of blip_retrieval.py:348-380: the gradient of this rank's slice is the SUM over the ranks of the
+    gradients of the gathered tensor (all_reduce), as the reference's GatherLayer does."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return _all_gather(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        import torch.distributed as dist
+        src = g.contiguous() if dist.get_backend() == "nccl" else g.cpu().contiguous()
+        dist.all_reduce(src)
+        B = g.shape[0] // dist.get_world_size()
+        r = dist.get_rank()
+        return src[r * B:(r + 1) * B].to(g.device)
+
+
+class _ItcLoss(torch.autograd.Function):
+    """mean over rows of one direction of the contrastive loss (madtp_itc_loss).  The gradient is formed in the forward, before
+    the queue is overwritten; backward only scales it by grad_out."""
+
+    @staticmethod
+    def forward(ctx, q, temp, q_m, keys_batch, queue, idx, idx_queue, alpha):
+        loss, dq, dtemp = hip.itc_loss(q.contiguous(), q_m.contiguous(), keys_batch.contiguous(), queue, idx, idx_queue,
+                                       temp.detach().reshape(1), alpha)
+        ctx.save_for_backward(dq, dtemp)
+        ctx.temp_shape = temp.shape
+        return loss.mean()
+
+    @staticmethod
+    def backward(ctx, g):
+        dq, dtemp = ctx.saved_tensors
+        return dq * g, (dtemp * g).reshape(ctx.temp_shape), None, None, None, None, None, None
 
 
 class BLIP_Retrieval(nn.Module):
@@ -48,14 +105,232 @@ class BLIP_Retrieval(nn.Module):
         self.itm_head = nn.Linear(text_width, 2)
         self.queue_size, self.momentum, self.negative_all_rank = queue_size, momentum, negative_all_rank
         self._cache = PreparedCache()
+        self.evaluate = evaluate
+        if evaluate:
+            return
+        # the training state of :67-93, the reference's names and order
+        self.criterion = nn.CosineEmbeddingLoss()
+        self.visual_encoder_m, vision_width = create_vit(vit, image_size, evaluate=evaluate, sd_dim=self.sd_dim)
+        self.vision_proj_m = nn.Linear(vision_width, embed_dim)
+        self.text_encoder_m = BertModel(config=med_config, add_pooling_layer=False, sd_dim=self.sd_dim)
+        self.text_proj_m = nn.Linear(text_width, embed_dim)
+        self.model_pairs = [[self.visual_encoder, self.visual_encoder_m], [self.vision_proj, self.vision_proj_m],
+                            [self.text_encoder, self.text_encoder_m], [self.text_proj, self.text_proj_m]]
+        self.copy_params()
+        self.register_buffer("image_queue", F.normalize(torch.randn(embed_dim, queue_size), dim=0))
+        self.register_buffer("text_queue", F.normalize(torch.randn(embed_dim, queue_size), dim=0))
+        self.register_buffer("idx_queue", torch.full((1, queue_size), -100))
+        self.register_buffer("ptr_queue", torch.zeros(1, dtype=torch.long))
+        self.temp = nn.Parameter(0.07 * torch.ones([]))
+        # itm_uniforms: None (torch.rand(2, B) on the device, seeded by torch.manual_seed) or a f32 [2,B] tensor of uniforms in
+        # [0,1) for the hard-negative draw - row 0 picks each text's negative image, row 1 each image's negative text
+        self.itm_uniforms = None
+        self._ema = hip.EmaTable()
+        self._ema_pairs = None       # [(param_m, param)] of momentum_pairs(), built at the first update
+        self._ptr_host = None        # host mirror of ptr_queue: (value, ptr_queue._version it was read / written at)
+        self._neg_flag = None        # device int32: set by madtp_itm_negatives when a row had no admissible negative
+        self._neg_flag_host = None   # pinned copy of it, read at the next forward after its event
+        self._neg_flag_event = None
+        self.last_negatives = None   # int64 [2,B] of the last forward (world columns): the drawn negative image / text
+
+    @staticmethod
+    def _remove_alpha(model):
+        return [param for name, param in model.named_parameters() if 'alpha' not in name]
+
+    def momentum_pairs(self):
+        """[(param, param_m)] of :287-300, paired by position after dropping names containing 'alpha' (remove_alpha)."""
+        return [(p, pm) for a, m in self.model_pairs for p, pm in zip(self._remove_alpha(a), m.parameters())]
+
+    @torch.no_grad()
+    def copy_params(self):  # :285-291
+        for p, pm in self.momentum_pairs():
+            pm.data.copy_(p.data)
+            pm.requires_grad = False
+
+    @torch.no_grad()
+    def _momentum_update(self):
+        """:293-300 p_m = p_m m + p (1 - m) for every pair in one launch (madtp_ema_update), in place.  The reference assigns new
+        storage; here the storage stays and the update epoch of every momentum parameter is bumped so that the prepared weights of
+        the momentum towers (runtime.PreparedCache) are rebuilt."""
+        if self._ema_pairs is None:
+            self._ema_pairs = [(pm, p) for p, pm in self.momentum_pairs()]
+        self._ema.update(self._ema_pairs, self.momentum)
+        for pm, _ in self._ema_pairs:
+            pm._madtp_steps = getattr(pm, "_madtp_steps", 0) + 1
 
     def forward(self, image, caption, alpha, idx, temperature=0, train=True):
-        raise NotImplementedError("BLIP_Retrieval.forward is the ITC/ITM training loss (momentum encoders, queues, negative "
-                                  "mining): out of scope; use blip_retrieval.evaluate() for the evaluation path")
+        """The training step of blip_retrieval.py:99-282 -> (loss_ita, loss_itm, loss_fdt, loss_fdt_m).  evaluate=False models only.
+
+        caption: {'input_ids', 'attention_mask'} tensors (or raw strings with model.tokenizer set), idx: int64 [B] image ids.
+        Student towers on the autograd routes of the HIP path; momentum towers (after the EMA, madtp_ema_update) on the inference
+        path under no_grad at the same temperature.  ITC: madtp_itc_loss per direction against [in-batch | queue] BEFORE the
+        queues advance (the gradient is formed there).  ITM: hard negatives drawn by madtp_itm_negatives at uniforms
+        `itm_uniforms` (default torch.rand on the device) - the inverse CDF of the masked softmax weights; a row with no
+        admissible negative (every column shares its id, where torch.multinomial raises) makes the NEXT forward raise.
+        With a process group: the momentum features and ids are gathered for the queue (it advances by world * B), and with
+        negative_all_rank the negatives are drawn from every rank's batch (image_embeds gathered with gradient; the ranks must
+        hold image tokens of one length).  Needs runtime.precision('fp32') or 'f16x3'; model.train() applies the reference's
+        dropout / DropPath with the counter-based masks (runtime.set_dropout_seed)."""
+        if self.evaluate:
+            raise NotImplementedError("BLIP_Retrieval(evaluate=True) is the evaluation model (compress_retrieval_dtp.py:350-373): "
+                                      "build it with evaluate=False to train, or use blip_retrieval.evaluate()")
+        from .backward import LinearFunction, _check_mode
+        _check_mode("BLIP_Retrieval.forward (training)")
+        require_gpu(image, "image")
+        dev = image.device
+        self._raise_pending_negative_error()
+        with torch.no_grad():
+            self.temp.clamp_(0.001, 0.5)
+        sd = self.space_dict
+        B = image.size(0)
+        world = _dist_world()
+        if self.queue_size % (world * B) != 0:  # :307 (checked on the host)
+            raise AssertionError(f"queue_size {self.queue_size} is not a multiple of the gathered batch {world * B}")
+
+        image_embeds, sd_img_ft = self.visual_encoder(image, space_dict=sd, temperature=temperature)  # :103
+        image_atts = torch.ones(image_embeds.size()[:-1], dtype=torch.long, device=dev)
+        image_feat = F.normalize(LinearFunction.apply(image_embeds[:, 0, :].contiguous(), self.vision_proj.weight,
+                                                      self.vision_proj.bias, hip.ACT_NONE), dim=-1)  # :105
+        ids, att = _tokens(self, caption, dev)  # :107-108
+        text_output, sd_txt_ft = self.text_encoder(ids, attention_mask=att, return_dict=True, mode='text', space_dict=sd,
+                                                   temperature=temperature)  # :110-113
+        text_feat = F.normalize(LinearFunction.apply(text_output.last_hidden_state[:, 0, :].contiguous(), self.text_proj.weight,
+                                                     self.text_proj.bias, hip.ACT_NONE), dim=-1)  # :114
+
+        idx = idx.to(dev).view(-1)
+        with torch.no_grad():  # :122-139 momentum features (the EMA first, as :123)
+            self._momentum_update()
+            image_embeds_m, sd_img_ft_m = self.visual_encoder_m(image, space_dict=sd, temperature=temperature)
+            image_feat_m = F.normalize(self._linear("vp_m", self.vision_proj_m, image_embeds_m[:, 0, :]), dim=-1)
+            text_output_m, sd_txt_ft_m = self.text_encoder_m(ids, attention_mask=att, return_dict=True, mode='text',
+                                                             space_dict=sd, temperature=temperature)
+            text_feat_m = F.normalize(self._linear("tp_m", self.text_proj_m, text_output_m.last_hidden_state[:, 0, :]), dim=-1)
+            image_feat_m, text_feat_m = image_feat_m.contiguous(), text_feat_m.contiguous()
+
+        # :116-150 ITC against [in-batch momentum features | queue] (the queue as it is BEFORE this step's enqueue)
+        idx_q = self.idx_queue[0]
+        loss_i2t = _ItcLoss.apply(image_feat, self.temp, image_feat_m, text_feat_m, self.text_queue, idx, idx_q, float(alpha))
+        loss_t2i = _ItcLoss.apply(text_feat, self.temp, text_feat_m, image_feat_m, self.image_queue, idx, idx_q, float(alpha))
+        loss_ita = (loss_i2t + loss_t2i) / 2
+
+        loss_fdt = loss_ita
+        loss_fdt_m = loss_ita
+        if temperature != 0 and sd_img_ft is not None and sd_txt_ft is not None and train:  # :154-162
+            loss_fdt = self._fdt(sd_img_ft, sd_txt_ft)
+        if temperature != 0 and sd_img_ft_m is not None and sd_txt_ft_m is not None and train:  # :164-171
+            with torch.no_grad():
+                loss_fdt_m = self._fdt(sd_img_ft_m, sd_txt_ft_m)
+
+        idxs = _all_gather(idx)  # :173-174
+        self._dequeue_and_enqueue(image_feat_m, text_feat_m, idxs)
+
+        # :176-282 ITM
+        encoder_input_ids = ids.clone()
+        encoder_input_ids[:, 0] = ENC_TOKEN_ID
+        output_pos, _ = self.text_encoder(encoder_input_ids, attention_mask=att, encoder_hidden_states=image_embeds,
+                                          encoder_attention_mask=image_atts, return_dict=True, space_dict=sd,
+                                          temperature=temperature)  # :180-187
+        if self.negative_all_rank and world > 1:
+            self._check_equal_lengths(image_embeds.shape[1])
+            with torch.no_grad():
+                image_feat_world = _all_gather(image_feat.detach().contiguous())
+                text_feat_world = _all_gather(text_feat.detach().contiguous())
+            image_embeds_world = _GatherWithGrad.apply(image_embeds)
+            input_ids_world = _all_gather(encoder_input_ids)
+            att_world = _all_gather(att)
+            idx_world = idxs
+        else:
+            image_feat_world, text_feat_world = image_feat.detach(), text_feat.detach()
+            image_embeds_world, input_ids_world, att_world, idx_world = image_embeds, encoder_input_ids, att, idx
+        neg = self._draw_negatives(image_feat.detach().contiguous(), text_feat.detach().contiguous(),
+                                   image_feat_world.contiguous(), text_feat_world.contiguous(), idx, idx_world.contiguous())
+        sel = neg.clamp_min(0)  # -1 (no admissible negative) is reported by the next forward; never used as an index
+        image_embeds_neg = image_embeds_world.index_select(0, sel[0])
+        text_ids_neg = input_ids_world.index_select(0, sel[1])
+        text_atts_neg = att_world.index_select(0, sel[1])
+
+        text_ids_all = torch.cat([encoder_input_ids, text_ids_neg], dim=0)  # :260-264
+        text_atts_all = torch.cat([att, text_atts_neg], dim=0)
+        image_embeds_all = torch.cat([image_embeds_neg, image_embeds], dim=0)
+        image_atts_all = torch.cat([image_atts, image_atts], dim=0)
+        output_neg, _ = self.text_encoder(text_ids_all, attention_mask=text_atts_all, encoder_hidden_states=image_embeds_all,
+                                          encoder_attention_mask=image_atts_all, return_dict=True, space_dict=sd,
+                                          temperature=temperature)  # :266-273
+        vl_embeddings = torch.cat([output_pos.last_hidden_state[:, 0, :], output_neg.last_hidden_state[:, 0, :]], dim=0)
+        vl_output = LinearFunction.apply(vl_embeddings.contiguous(), self.itm_head.weight, self.itm_head.bias, hip.ACT_NONE)
+        itm_labels = torch.cat([torch.ones(B, dtype=torch.long), torch.zeros(2 * B, dtype=torch.long)], dim=0).to(dev)
+        loss_itm = F.cross_entropy(vl_output, itm_labels)  # :280
+        return loss_ita, loss_itm, loss_fdt, loss_fdt_m
+
+    def _fdt(self, sd_img_ft, sd_txt_ft):
+        si = sd_img_ft / (sd_img_ft.norm(dim=-1, keepdim=True) + 1e-10)
+        st = sd_txt_ft / (sd_txt_ft.norm(dim=-1, keepdim=True) + 1e-10)
+        si, st = si.reshape(-1, self.sd_dim), st.reshape(-1, self.sd_dim)
+        labels = torch.ones(si.shape[0], device=st.device).long()
+        return self.criterion(si, st, labels)
+
+    def _check_equal_lengths(self, n):
+        """The reference all_gathers image_embeds [B, n, 768]: undefined when pruning left the ranks different n.  Decided
+        collectively before any gather, so that every rank raises together."""
+        import torch.distributed as dist
+        from . import dist as mdist
+        dev = "cuda" if dist.get_backend() == "nccl" else "cpu"  # NCCL / RCCL reduce device tensors only
+        lo, hi = mdist.min_over_ranks(float(n), device=dev), mdist.max_over_ranks(float(n), device=dev)
+        if lo != hi:
+            raise RuntimeError(f"negative_all_rank: the ranks hold image tokens of different lengths ({int(lo)} .. {int(hi)}) after "
+                               "pruning; the reference's all_gather of image_embeds is undefined then (use temperature 0 or "
+                               "negative_all_rank=False)")
+
+    @torch.no_grad()
+    def _dequeue_and_enqueue(self, image_feat_m, text_feat_m, idxs):
+        """:302-322 with the pointer mirrored on the host (no int(ptr_queue) sync): stream-ordered after the ITC kernels."""
+        image_feats, text_feats = _all_gather(image_feat_m), _all_gather(text_feat_m)
+        n = image_feats.shape[0]
+        if self._ptr_host is None or self._ptr_host[1] != self.ptr_queue._version:
+            self._ptr_host = (int(self.ptr_queue[0]), self.ptr_queue._version)
+        ptr = self._ptr_host[0]
+        assert self.queue_size % n == 0
+        if ptr % n != 0:
+            ptr = (ptr // n) * n
+        self.image_queue[:, ptr:ptr + n] = image_feats.T
+        self.text_queue[:, ptr:ptr + n] = text_feats.T
+        self.idx_queue[:, ptr:ptr + n] = idxs.view(1, -1)
+        ptr = (ptr + n) % self.queue_size
+        self.ptr_queue.fill_(ptr)
+        self._ptr_host = (ptr, self.ptr_queue._version)
+
+    def _draw_negatives(self, image_feat, text_feat, image_feat_world, text_feat_world, idx, idx_world):
+        B = image_feat.shape[0]
+        dev = image_feat.device
+        if self._neg_flag is None or self._neg_flag.device != dev:
+            self._neg_flag = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._neg_flag_host = torch.zeros(1, dtype=torch.int32).pin_memory()
+        u = self.itm_uniforms
+        if u is None:
+            u = torch.rand(2, B, device=dev)
+        u = u.to(device=dev, dtype=torch.float32).contiguous()
+        neg = hip.itm_negatives(image_feat, text_feat, image_feat_world, text_feat_world, idx.contiguous(), idx_world,
+                                self.temp.detach().reshape(1), u, self._neg_flag)
+        self._neg_flag_host.copy_(self._neg_flag, non_blocking=True)
+        self._neg_flag_event = torch.cuda.Event()
+        self._neg_flag_event.record()
+        self.last_negatives = neg
+        return neg
+
+    def _raise_pending_negative_error(self):
+        if self._neg_flag_event is None:
+            return
+        self._neg_flag_event.synchronize()
+        self._neg_flag_event = None
+        if int(self._neg_flag_host[0]) != 0:
+            self._neg_flag.zero_()
+            self._neg_flag_host.zero_()
+            raise RuntimeError("BLIP_Retrieval: in the previous step a row had no admissible hard negative (every candidate shared "
+                               "its idx; torch.multinomial raises there) - its ITM pair was drawn from column 0")
 
     # ---- the small Linears of the evaluation path on the library GEMM ----
     def _linear(self, key, lin, x32):
-        l = lin_of(self._cache, key, [lin])
+        l = lin_of(self._cache, key, [lin])  # (the momentum projections: the cache follows their update epoch)
         return hip.gemm(to_compute(x32.contiguous()), l.w, l.b, out_dtype=torch.float32, n=l.n)
 
     def project_image(self, cls_rows):

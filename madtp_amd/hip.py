@@ -13,7 +13,7 @@ import torch
 F32, BF16, F16S, F16 = 0, 1, 2, 3  # F16S: f16-split operand planes of the fp32-accurate GEMM (include/madtp_hip.h), torch.float16
 #                                    F16: plain IEEE f16 operands (the "f16" fast mode), see set_lp_format below
 ACT_NONE, ACT_GELU, ACT_QUICK_GELU, ACT_RELU = 0, 1, 2, 3
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libmadtp_hip.so")
@@ -118,6 +118,12 @@ _SIGS = {
     "madtp_colsum": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "madtp_act_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     "madtp_layernorm_bwd": (c_int, [c_void_p] * 8 + [c_int, c_int, c_float, c_void_p]),
+    # retrieval training step (csrc/retrieval.hip)
+    "madtp_itc_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "madtp_itc_loss": (c_int, [c_void_p] * 7 + [c_float] + [c_void_p] * 4 + [c_size_t, c_int, c_int, c_int, c_void_p]),
+    "madtp_ema_blocks": (c_int, [ctypes.c_int64]),
+    "madtp_ema_update": (c_int, [c_void_p, c_int, c_int, c_float, c_float, c_void_p]),
+    "madtp_itm_negatives": (c_int, [c_void_p] * 10 + [c_int, c_int, c_int, c_void_p]),
     "madtp_token_gather_bwd": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p]),
     "madtp_token_score_bwd": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4
                               + [c_int, c_int, c_int, c_void_p]),
@@ -1419,3 +1425,97 @@ def bert_encoder(weights, hidden, hidden_lp, mask2d, qargs, temperature, cross_m
            "madtp_bert_encoder")
     run.keep = (hidden, hidden_lp, mask2d, wstructs, qargs, enc0, enc1, enc_mask0, enc_mask1, kv_pre0, kv_pre1, kv_index)
     return run
+
+
+# ---- retrieval training step (include/madtp_hip.h madtp_itc_loss / madtp_ema_update / madtp_itm_negatives) --------------------
+def _gpu_f32(t, name, dims):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == dims and t.is_contiguous()):
+        raise RuntimeError(f"{name}: a contiguous GPU f32 tensor of {dims} dimensions is required")
+
+
+def _gpu_i64(t, name):
+    if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()):
+        raise RuntimeError(f"{name}: a contiguous GPU int64 tensor is required")
+
+
+def itc_loss(q, q_m, keys_batch, queue, idx, idx_queue, temp, alpha):
+    """One direction of the contrastive loss (madtp_itc_loss): q, q_m, keys_batch f32 [B,D]; queue f32 [D,Q]; idx int64 [B];
+    idx_queue int64 [Q]; temp f32 [] or [1] on the device -> (loss [B], dq [B,D] = d mean(loss)/dq, dtemp [1])."""
+    for t, n in ((q, "q"), (q_m, "q_m"), (keys_batch, "keys_batch"), (queue, "queue")):
+        _gpu_f32(t, f"itc_loss: {n}", 2)
+    _gpu_i64(idx, "itc_loss: idx")
+    _gpu_i64(idx_queue, "itc_loss: idx_queue")
+    if not (temp.is_cuda and temp.dtype == torch.float32 and temp.numel() == 1):
+        raise RuntimeError("itc_loss: temp must be a one-element GPU f32 tensor")
+    B, D = q.shape
+    Q = queue.shape[1]
+    if q_m.shape != (B, D) or keys_batch.shape != (B, D) or queue.shape[0] != D or idx.numel() != B or idx_queue.numel() != Q:
+        raise RuntimeError("itc_loss: shapes disagree")
+    lib = load()
+    ws_bytes = int(lib.madtp_itc_workspace(B, D, Q))
+    ws = torch.empty(max(ws_bytes, 4) // 4 + 1, dtype=torch.float32, device=q.device)
+    loss = torch.empty(B, dtype=torch.float32, device=q.device)
+    dq = torch.empty(B, D, dtype=torch.float32, device=q.device)
+    dtemp = torch.empty(1, dtype=torch.float32, device=q.device)
+    _check(lib.madtp_itc_loss(_p(q), _p(q_m), _p(keys_batch), _p(queue) if Q else 0, _p(idx), _p(idx_queue) if Q else 0, _p(temp),
+                              float(alpha), _p(loss), _p(dq), _p(dtemp), _p(ws), ws.numel() * 4, B, D, Q, _stream()), "madtp_itc_loss")
+    return loss, dq, dtemp
+
+
+class EmaTable:
+    """Device pointer table of madtp_ema_update for a list of (momentum, source) f32 parameter pairs.  The pairs are validated
+    when the table is (re)built; each update compares only the data pointers (a list of ints) to notice an optimizer,
+    `.to()` or load_state_dict that assigned new storage."""
+
+    def __init__(self):
+        self._ptrs, self._table, self._blocks = None, None, 0
+
+    def update(self, pairs, m):
+        ptrs = [t.data_ptr() for pair in pairs for t in pair]
+        lib = load()
+        if ptrs != self._ptrs:
+            for pm, p in pairs:
+                if not (pm.is_cuda and pm.dtype == torch.float32 and pm.is_contiguous() and p.shape == pm.shape
+                        and p.dtype == pm.dtype and p.is_contiguous() and p.device == pm.device):
+                    raise RuntimeError("ema_update: every pair must be two contiguous GPU f32 tensors of one shape")
+            first, nb = [], 0
+            for pm, _ in pairs:
+                first.append(nb)
+                nb += int(lib.madtp_ema_blocks(pm.numel()))
+            rows = [ptrs[0::2], ptrs[1::2], [pm.numel() for pm, _ in pairs], first]
+            self._table = torch.tensor(rows, dtype=torch.int64).to(pairs[0][0].device)
+            self._ptrs, self._blocks = ptrs, nb
+            self._n = len(pairs)
+            self._mf = None
+        if self._mf is None or self._mf[0] != m:
+            # torch's scalar multiply: the f32 value of m, and of (1. - m) formed in double as in Python
+            self._mf = (m, float(torch.tensor(m, dtype=torch.float32)), float(torch.tensor(1.0 - m, dtype=torch.float32)))
+        if self._blocks:
+            _check(lib.madtp_ema_update(_p(self._table), self._n, self._blocks, self._mf[1], self._mf[2], _stream()),
+                   "madtp_ema_update")
+
+    def launch_only(self):
+        """the kernel alone on the current table (timing of tools/retrieval_train_ab.py)"""
+        _check(load().madtp_ema_update(_p(self._table), self._n, self._blocks, self._mf[1], self._mf[2], _stream()),
+               "madtp_ema_update")
+
+
+def itm_negatives(image_feat, text_feat, image_feat_world, text_feat_world, idx, idx_world, temp, u, flag):
+    """madtp_itm_negatives -> int64 [2,B]: row 0 the negative image (column of image_feat_world) of every text, row 1 the
+    negative text of every image; -1 where every column shares the row's id (the device int32 `flag` is then set to 1)."""
+    for t, n in ((image_feat, "image_feat"), (text_feat, "text_feat"), (image_feat_world, "image_feat_world"),
+                 (text_feat_world, "text_feat_world"), (u, "u")):
+        _gpu_f32(t, f"itm_negatives: {n}", 2)
+    _gpu_i64(idx, "itm_negatives: idx")
+    _gpu_i64(idx_world, "itm_negatives: idx_world")
+    B, D = image_feat.shape
+    Bw = image_feat_world.shape[0]
+    if (text_feat.shape != (B, D) or image_feat_world.shape != (Bw, D) or text_feat_world.shape != (Bw, D) or u.shape != (2, B)
+            or idx.numel() != B or idx_world.numel() != Bw):
+        raise RuntimeError("itm_negatives: shapes disagree")
+    if not (flag.is_cuda and flag.dtype == torch.int32 and temp.is_cuda and temp.dtype == torch.float32 and temp.numel() == 1):
+        raise RuntimeError("itm_negatives: flag must be a GPU int32 tensor and temp a one-element GPU f32 tensor")
+    neg = torch.empty(2, B, dtype=torch.int64, device=image_feat.device)
+    _check(load().madtp_itm_negatives(_p(image_feat), _p(text_feat), _p(image_feat_world), _p(text_feat_world), _p(idx), _p(idx_world),
+                                      _p(temp), _p(u), _p(neg), _p(flag), B, Bw, D, _stream()), "madtp_itm_negatives")
+    return neg

@@ -1193,6 +1193,120 @@ def pos_embed_case(name, width=64, seed=0):
     np.savez_compressed(os.path.join(GOLD, name + ".npz"), checkpoint=ck.numpy(), resized=out.numpy())
 
 
+def retr_train_case(name, B, size, L, temperature, idx, alpha, queue_size, seed=0, pad_tail=2, nsample=32, lr=0.05):
+    """The reference's OWN retrieval training step (models/blip_retrieval.py:99-282, BLIP_Retrieval(evaluate=False), model.eval():
+    no dropout / DropPath) at world 1: student ViT + MED text / multimodal towers, momentum towers after the EMA, ITC against the
+    feature queues, in-batch hard negatives for ITM, dequeue-and-enqueue; loss = loss_ita + loss_itm + 0.1 (loss_fdt + loss_fdt_m)
+    as compress_retrieval_dtp.py:64-65.  torch.multinomial is replaced - for this recording only - by the inverse CDF at seeded
+    uniforms (the first j with cumsum(w)_j > u sum(w)), the rule the HIP path draws by; the uniforms are stored.  Then
+    torch.optim.SGD(lr) steps on the gradients and a SECOND forward is recorded (its four losses only)."""
+    import models.blip_retrieval as rbr
+    from madtp_amd import harness
+    ref_shims.patch_tokenizer(rbr)
+    rbr.concat_all_gather = lambda t: t  # world 1 (the reference's all_gather over one rank)
+    torch.manual_seed(seed)
+    model = rbr.BLIP_Retrieval(image_size=size, vit="base", queue_size=queue_size, negative_all_rank=False, evaluate=False)
+    model.eval()
+    keys = list(model.state_dict().keys())
+    pairing = []
+    for a_mod, m_mod in model.model_pairs:
+        an = [n for n, p in a_mod.named_parameters() if "alpha" not in n]
+        mn = [n for n, _ in m_mod.named_parameters()]
+        a_pre = [k for k, m in model.named_modules() if m is a_mod][0]
+        m_pre = [k for k, m in model.named_modules() if m is m_mod][0]
+        pairing += [f"{a_pre}.{x}|{m_pre}.{y}" for x, y in zip(an, mn)]
+    sd = synth.fill_state_dict(model, seed)
+    # the buffers the HIP test rebuilds from the fixture itself: unit-norm queue columns, ids (some equal to batch ids), ptr, temp
+    g = torch.Generator().manual_seed(1000 + seed)
+    sd["image_queue"] = torch.nn.functional.normalize(torch.randn(256, queue_size, generator=g), dim=0)
+    sd["text_queue"] = torch.nn.functional.normalize(torch.randn(256, queue_size, generator=g), dim=0)
+    iq = torch.full((1, queue_size), -100, dtype=torch.long)
+    iq[0, 1] = idx[0]
+    iq[0, queue_size // 2] = idx[-1]
+    iq[0, 2] = 11
+    sd["idx_queue"] = iq
+    sd["ptr_queue"] = torch.tensor([B], dtype=torch.long)
+    sd["temp"] = torch.tensor(0.07)
+    model.load_state_dict(sd, strict=True)
+    momentum = {id(p) for _, m in model.model_pairs for p in m.parameters()}
+    images = synth.synth_images(B, size, seed)
+    ids = synth.synth_token_ids(B, L, seed, first_id=101)
+    att = harness.padded_mask(B, L, pad_tail)
+    idx_t = torch.tensor(idx, dtype=torch.long)
+    gu = torch.Generator().manual_seed(2000 + seed)
+    u = torch.rand(2, B, generator=gu)
+    drawn, calls = [], [0]
+    orig_multinomial = torch.multinomial
+
+    def inverse_cdf(w, n):
+        k = calls[0]
+        calls[0] += 1
+        c = torch.cumsum(w, 0)
+        j = int(torch.nonzero(c > u[k // B, k % B] * c[-1])[0, 0])
+        drawn.append(j)
+        return torch.tensor([j])
+
+    lens = {"vit": [], "txt": [], "vit_m": [], "txt_m": []}
+    hooks = []
+    for tag, enc in (("vit", model.visual_encoder), ("vit_m", model.visual_encoder_m)):
+        for blk in enc.blocks:
+            hooks.append(blk.register_forward_hook(lambda m, a, o, t=tag: lens[t].append(o.shape[1])))
+    for tag, enc in (("txt", model.text_encoder), ("txt_m", model.text_encoder_m)):
+        for lay in enc.encoder.layer:
+            hooks.append(lay.register_forward_hook(lambda m, a, o, t=tag: lens[t].append(o[0].shape[1])))
+    for p_ in model.parameters():
+        if id(p_) not in momentum:
+            p_.requires_grad_(True)
+        p_.grad = None
+    caption = {"input_ids": ids, "attention_mask": att}
+    torch.multinomial = inverse_cdf
+    try:
+        losses = model(images, caption, alpha, idx_t, temperature=temperature, train=True)
+    finally:
+        torch.multinomial = orig_multinomial
+    for h in hooks:
+        h.remove()
+    loss = losses[0] + losses[1] + 0.1 * losses[2] + 0.1 * losses[3]
+    loss.backward()
+    rec = {"kind": "retr_train", "B": B, "size": size, "L": L, "temperature": np.float64(temperature), "seed": seed,
+           "pad_tail": pad_tail, "nsample": nsample, "alpha": np.float64(alpha), "idx": np.array(idx), "queue_size": queue_size,
+           "lr": np.float64(lr), "momentum": np.float64(model.momentum), "state_dict_keys": np.array(keys),
+           "pairing": np.array(pairing), "u": u.numpy(), "neg": np.array(drawn).reshape(2, B),
+           "init_image_queue": sd["image_queue"].numpy(), "init_text_queue": sd["text_queue"].numpy(),
+           "init_idx_queue": sd["idx_queue"].numpy(), "init_ptr": int(sd["ptr_queue"][0]), "init_temp": np.float64(0.07),
+           "losses": np.array([float(x) for x in losses], dtype=np.float64),
+           "image_queue": model.image_queue.numpy().copy(), "text_queue": model.text_queue.numpy().copy(),
+           "idx_queue": model.idx_queue.numpy().copy(), "ptr": int(model.ptr_queue[0])}  # (copies: the second step writes on)
+    for t, v in lens.items():
+        rec[f"{t}_lens"] = np.array(v)
+    n = 0
+    for k, v in model.named_parameters():
+        if v.grad is None:
+            continue
+        flat = v.grad.detach().reshape(-1)
+        ix = grad_sample_index(flat.numel(), nsample)
+        rec[f"g_{k}_sample"] = flat[torch.from_numpy(ix)].numpy()
+        rec[f"g_{k}_norm"] = np.float64(flat.double().norm().item())
+        n += 1
+    for k, v in model.named_parameters():
+        if id(v) in momentum:
+            flat = v.detach().reshape(-1)
+            rec[f"m_{k}"] = flat[torch.from_numpy(grad_sample_index(flat.numel(), 16, stride=104729))].numpy()
+    torch.optim.SGD([p_ for p_ in model.parameters() if p_.grad is not None], lr=lr).step()
+    torch.multinomial = inverse_cdf
+    calls[0] = 0
+    try:
+        with torch.no_grad():
+            losses2 = model(images, caption, alpha, idx_t, temperature=temperature, train=True)
+    finally:
+        torch.multinomial = orig_multinomial
+    rec["losses2"] = np.array([float(x) for x in losses2], dtype=np.float64)
+    rec["neg2"] = np.array(drawn[2 * B:]).reshape(2, B)
+    np.savez_compressed(os.path.join(GOLD, name + ".npz"), **rec)
+    print(f"[{name}] T={temperature} lens={ {t: v for t, v in lens.items()} } losses={rec['losses'].round(5).tolist()} "
+          f"losses2={rec['losses2'].round(5).tolist()} neg={rec['neg'].tolist()} {n} gradients")
+
+
 CASES = {
     "pos_embed_384": lambda: pos_embed_case("pos_embed_384"),
     "medopts_b2": lambda: med_layer_options_case("medopts_b2", 2, 35, 10, 30.0, pad_tail=1, Lp=20),
@@ -1238,6 +1352,9 @@ CASES = {
     "trainstep_vqa_b2": lambda: vqa_train_case("trainstep_vqa_b2", 2, 96, 20, 20.0, [2, 1], 6),
     "decgrad_b3": lambda: decoder_grad_case("decgrad_b3", 3, 8, 12),
     "trainstep_nlvr_b2": lambda: nlvr_model_grad_case("trainstep_nlvr_b2", 2, 96, 35, 30.0, pad_tail=0, nsample=64, train=True),
+    # the retrieval training step (BLIP_Retrieval.forward, evaluate=False): duplicate ids, ids shared with the queue, T = 20 and 0
+    "trainstep_retr_b3_T20": lambda: retr_train_case("trainstep_retr_b3_T20", 3, 96, 20, 20.0, [5, 7, 5], 0.4, 12),
+    "trainstep_retr_b4_T0": lambda: retr_train_case("trainstep_retr_b4_T0", 4, 96, 16, 0.0, [3, 8, 9, 4], 0.4, 12, seed=1),
     "modelgrad_nlvr_b2": lambda: nlvr_model_grad_case("modelgrad_nlvr_b2", 2, 96, 35, 30.0, pad_tail=0, nsample=64),
     "nlvrgrad_b3_l3": lambda: nlvr_layer_grad_case("nlvrgrad_b3_l3", 3, 35, 30.0, layer=3, pad_tail=3),
     "nlvrgrad_b3_l7": lambda: nlvr_layer_grad_case("nlvrgrad_b3_l7", 3, 35, 30.0, layer=7, pad_tail=3),
