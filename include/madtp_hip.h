@@ -141,7 +141,9 @@ int madtp_layernorm(const float* x, const float* gamma, const float* beta, float
                     int rows, int dim, float eps, void* stream);
 
 /* im2col of non-overlapping patches for the patch-embedding GEMM (timm PatchEmbed Conv2d k=s=P, call site
- * vit.py:241-242,283): img f32 [B,3,S,S] -> cols [B*(S/P)^2, 3*P*P] (dtype out_dtype), column = c*P*P+ky*P+kx. */
+ * vit.py:241-242,283): img f32 [B,3,S,S] -> cols [B*(S/P)^2, Kp] (dtype out_dtype; F16S: planes [P0 | P1], 2*Kp wide),
+ * column = c*P*P+ky*P+kx, Kp = 3*P*P rounded up to a multiple of 64 (the GEMM's K granularity) with a zero tail
+ * (P = 16: Kp = 768, no tail; P = 14: Kp = 640).  Any P with S % P == 0. */
 int madtp_patchify(const float* img, void* cols, int B, int S, int P, int out_dtype, void* stream);
 
 /* x[b,0,:] = cls + pos[0]; x[b,1+p,:] = patches[b*np+p,:] + pos[1+p]   (vit.py:285-289). All f32. */

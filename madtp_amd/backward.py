@@ -1345,7 +1345,13 @@ class ClipPatchTokensFunction(torch.autograd.Function):
     def forward(ctx, img, w, cls, pos, patch):
         ctx.mode = _mode()
         cols = hip.patchify(img, patch, torch.float32)
-        wp, _ = _f32_wb(w.reshape(w.shape[0], -1), None)
+        w2 = w.reshape(w.shape[0], -1)
+        if cols.shape[1] != w2.shape[1]:  # patch sizes with a zero tail in the patchify rows (ViT-L/14: 588 -> 640 columns)
+            kp = cols.shape[1]
+            wp = _cached(("pwk", w.data_ptr(), _x3(), kp), [w],
+                         _versioned(lambda: _pad_w(torch.nn.functional.pad(w2.detach(), (0, kp - w2.shape[1])))))
+        else:
+            wp, _ = _f32_wb(w2, None)
         patches = _gemm(cols, wp, None, out_dtype=torch.float32, n=w.shape[0])
         B = img.shape[0]
         ctx.np_, ctx.patch = patches.shape[0] // B, patch
@@ -1362,7 +1368,8 @@ class ClipPatchTokensFunction(torch.autograd.Function):
             dcls = dpos[0].clone()
             dpatch = dx[:, 1:, :].reshape(B * ctx.np_, D).contiguous()
             cols = hip.patchify(img, ctx.patch, torch.float32)
-            dw = wgrad(dpatch, cols).view_as(w)
+            dw = wgrad(dpatch, cols)  # [width, Kp]: the zero-tail columns' gradient is dropped
+            dw = (dw if dw.shape[1] == w[0].numel() else dw[:, :w[0].numel()]).reshape(w.shape)
         return None, dw, dcls, dpos, None
 
 

@@ -168,6 +168,13 @@ class VisionTransformer(nn.Module):
         self.proj = nn.Parameter(scale * torch.randn(width, output_dim))
         self._cache = PreparedCache()
 
+    def conv_weight_cols(self):
+        """conv1.weight as the patch-embedding GEMM's [width, Kp] operand (hip.patch_cols): zero columns past 3 * P^2, which
+        meet the zero tail of the patchify rows (ViT-L/14: 588 -> 640; ViT-B/16: 768, no tail)"""
+        w = self.conv1.weight.detach().reshape(self.conv1.weight.shape[0], -1).float()
+        kp = hip.patch_cols(self.patch_size)
+        return w if kp == w.shape[1] else torch.nn.functional.pad(w, (0, kp - w.shape[1]))
+
     def forward(self, x: torch.Tensor, space_dict=None, temperature=0, max_keep=1):
         img = as_f32_contig(require_gpu(x, "image"))
         B = img.shape[0]
@@ -176,7 +183,7 @@ class VisionTransformer(nn.Module):
             from .backward import clip_vision_forward_with_grad  # (the tower under autograd)
             return clip_vision_forward_with_grad(self, img, space_dict, temperature, max_keep)
         cdt = compute_dtype()
-        conv = self._cache.get(("conv", cdt), [self.conv1.weight], lambda: prepare_linear([self.conv1.weight], None, cdt))
+        conv = self._cache.get(("conv", cdt), [self.conv1.weight], lambda: prepare_linear([self.conv_weight_cols()], None, cdt))
         cols = hip.patchify(img, self.patch_size, cdt)
         patches = hip.gemm(cols, conv.w, None, out_dtype=torch.float32, n=conv.n)  # :293-295
         np_ = patches.shape[0] // B

@@ -130,6 +130,62 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
     }
 }
 
+// patch sizes whose image rows are not 16-byte aligned (P % 4 != 0, e.g. ViT-L/14) and/or whose 3*P*P is not a multiple of
+// the GEMM's K granularity: rows of Kp (a multiple of 64) columns, the tail Kp - 3*P*P zero.  One thread per 4 consecutive
+// output columns; with an even P each pair of columns lies in one image row at an even offset (an 8-byte load), else scalar loads.
+template <typename T, bool EVEN>
+__global__ __launch_bounds__(256) void patchify_pad_kernel(const float* __restrict__ img, T* __restrict__ cols, int S, int P,
+                                                           int Kp, size_t total4) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total4) return;
+    const int kq = Kp / 4;
+    const int kcols = 3 * P * P;
+    const int g = S / P;
+    const int col0 = (int)(i % kq) * 4;
+    const size_t prow = i / kq;
+    const int px = (int)(prow % g), py = (int)((prow / g) % g);
+    const size_t b = prow / ((size_t)g * g);
+    const float* base = img + b * 3 * S * S + (size_t)py * P * S + (size_t)px * P;
+    float v[4];
+    if constexpr (EVEN) {
+#pragma unroll
+        for (int j = 0; j < 4; j += 2) {
+            const int col = col0 + j;
+            float2 t = make_float2(0.f, 0.f);
+            if (col < kcols) {  // kcols is even: col + 1 < kcols too
+                const int kx = col % P, ky = (col / P) % P, c = col / (P * P);
+                t = *(const float2*)(base + ((size_t)c * S + ky) * S + kx);
+            }
+            v[j] = t.x; v[j + 1] = t.y;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int col = col0 + j;
+            v[j] = 0.f;
+            if (col < kcols) {
+                const int kx = col % P, ky = (col / P) % P, c = col / (P * P);
+                v[j] = base[((size_t)c * S + ky) * S + kx];
+            }
+        }
+    }
+    const f32x4 f = (f32x4){v[0], v[1], v[2], v[3]};
+    if constexpr (std::is_same<T, _Float16>::value) {  // f16-split planes [P0 | P1], row stride 2*Kp
+        f16x4 h, l;
+        split_f16x4(f, h, l);
+        _Float16* o = cols + prow * 2 * Kp + col0;
+        *(f16x4*)o = h;
+        *(f16x4*)(o + Kp) = l;
+    } else if constexpr (std::is_same<T, F16Plain>::value) {  // plain f16 (MADTP_F16)
+        *(bf16x4*)((bf16_t*)cols + prow * Kp + col0) = pack_f16x4(f);
+    } else if constexpr (std::is_same<T, float>::value) {
+        *(f32x4*)(cols + prow * Kp + col0) = f;
+    } else {
+        T* o = cols + prow * Kp + col0;
+        o[0] = from_f32<T>(v[0]); o[1] = from_f32<T>(v[1]); o[2] = from_f32<T>(v[2]); o[3] = from_f32<T>(v[3]);
+    }
+}
+
 __global__ __launch_bounds__(256) void assemble_kernel(const float* __restrict__ patches, const float* __restrict__ cls,
                                                        const float* __restrict__ pos, float* __restrict__ x, int B, int np,
                                                        int dim4, size_t total4) {
@@ -286,9 +342,30 @@ extern "C" int madtp_bert_embed(const int64_t* ids, const float* word_emb, const
     return 0;
 }
 
+template <typename T>
+static void patchify_pad_launch(const float* img, void* cols, int B, int S, int P, int Kp, hipStream_t stream) {
+    const size_t total4 = (size_t)B * (S / P) * (S / P) * (Kp / 4);
+    const dim3 grid((unsigned)((total4 + 255) / 256));
+    if (P % 2 == 0)
+        hipLaunchKernelGGL((patchify_pad_kernel<T, true>), grid, dim3(256), 0, stream, img, (T*)cols, S, P, Kp, total4);
+    else
+        hipLaunchKernelGGL((patchify_pad_kernel<T, false>), grid, dim3(256), 0, stream, img, (T*)cols, S, P, Kp, total4);
+}
+
 extern "C" int madtp_patchify(const float* img, void* cols, int B, int S, int P, int out_dtype, void* stream) {
     if (!img || !cols || B <= 0 || S <= 0 || P <= 0) return MADTP_E_BADARG;
-    if (S % P || P % 4) return MADTP_E_SHAPE;
+    if (S % P) return MADTP_E_SHAPE;
+    if (out_dtype != MADTP_F32 && out_dtype != MADTP_BF16 && out_dtype != MADTP_F16 && out_dtype != MADTP_F16S) return MADTP_E_DTYPE;
+    const int kcols = 3 * P * P;
+    const int Kp = (kcols + 63) / 64 * 64;
+    if (P % 4 || Kp != kcols) {  // rows of Kp columns with a zero tail (image rows at 8- or 4-byte offsets)
+        if (out_dtype == MADTP_F32) patchify_pad_launch<float>(img, cols, B, S, P, Kp, (hipStream_t)stream);
+        else if (out_dtype == MADTP_BF16) patchify_pad_launch<bf16_t>(img, cols, B, S, P, Kp, (hipStream_t)stream);
+        else if (out_dtype == MADTP_F16) patchify_pad_launch<F16Plain>(img, cols, B, S, P, Kp, (hipStream_t)stream);
+        else patchify_pad_launch<_Float16>(img, cols, B, S, P, Kp, (hipStream_t)stream);
+        MADTP_LAUNCH_CHECK();
+        return 0;
+    }
     const size_t total4 = (size_t)B * 3 * S * S / 4;
     const dim3 grid((unsigned)((total4 + 255) / 256));
     if (out_dtype == MADTP_F32)
@@ -297,10 +374,8 @@ extern "C" int madtp_patchify(const float* img, void* cols, int B, int S, int P,
         hipLaunchKernelGGL(patchify_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, img, (bf16_t*)cols, B, S, P, total4);
     else if (out_dtype == MADTP_F16)
         hipLaunchKernelGGL(patchify_kernel<F16Plain>, grid, dim3(256), 0, (hipStream_t)stream, img, (F16Plain*)cols, B, S, P, total4);
-    else if (out_dtype == MADTP_F16S)
-        hipLaunchKernelGGL(patchify_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, img, (_Float16*)cols, B, S, P, total4);
     else
-        return MADTP_E_DTYPE;
+        hipLaunchKernelGGL(patchify_kernel<_Float16>, grid, dim3(256), 0, (hipStream_t)stream, img, (_Float16*)cols, B, S, P, total4);
     MADTP_LAUNCH_CHECK();
     return 0;
 }

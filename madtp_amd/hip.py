@@ -471,11 +471,18 @@ def layernorm(x, gamma, beta, eps, want_f32=True, want_bf16=False, lp=None):
     return y32, ylp
 
 
+def patch_cols(patch, channels=3):
+    """width of a patchify row: channels * patch^2 rounded up to the GEMM's K granularity (64), the tail zero (768 at P = 16,
+    640 at P = 14)"""
+    return (channels * patch * patch + 63) // 64 * 64
+
+
 def patchify(img, patch, out_dtype):
+    """im2col of the non-overlapping patches -> [B * (S/P)^2, patch_cols(P)] (f16-split planes: twice as wide)."""
     _req(img, torch.float32, "img")
     B, C, S, _ = img.shape
     g = S // patch
-    kc = C * patch * patch
+    kc = patch_cols(patch, C)
     cols = torch.empty((B * g * g, 2 * kc if out_dtype == torch.float16 else kc), device=img.device, dtype=out_dtype)
     _check(load().madtp_patchify(_p(img), _p(cols), B, S, patch, _dt(cols), _stream()), "madtp_patchify")
     return cols

@@ -210,10 +210,24 @@ class Clip(Workload):
     name, default_batch, p = "clip", 128, 0.5
     size, ctx = 224, 77
     default_inflight = 1  # both towers fill the chip: 17.1-18.0 k serial; two in flight gave 15.9 k to 22.8 k from run to run, three 15 k
+    # clip/model.py build_model geometries: (patch, vision width, vision layers, embed_dim, text width); heads = width / 64,
+    # 12 text layers.  ViT-L/14 is the model of the reference's configs/retrieval_{coco,flickr}_clip.yaml (image_size 336)
+    ARCHS = {"ViT-B/16": (16, 768, 12, 512, 512), "ViT-L/14": (14, 1024, 24, 768, 768)}
+
+    def __init__(self, arch="ViT-B/16", size=None):
+        if arch not in self.ARCHS:
+            raise ValueError(f"unknown CLIP architecture {arch!r}: one of {sorted(self.ARCHS)}")
+        self.arch = arch
+        self.patch, self.width, self.layers, self.embed_dim, self.text_width = self.ARCHS[arch]
+        if size is not None:
+            self.size = size
+
+    def shapes(self):
+        return specs.clip_shapes(self.size, self.patch, self.width, self.layers, self.embed_dim, self.text_width, 12)
 
     def build(self, device="cuda"):
         from .clip_model import build_model
-        return build_model(specs.synth_weights(specs.clip_shapes(self.size), 0, device=device), evaluate=True).eval().to(device)
+        return build_model(specs.synth_weights(self.shapes(), 0, device=device), evaluate=True).eval().to(device)
 
     def inputs(self, B, seed=0, device="cuda"):
         return synth.synth_images(B, self.size, seed, device=device), synth.synth_clip_tokens(B, self.ctx, seed).to(device)
@@ -228,17 +242,18 @@ class Clip(Workload):
         return hip.gemm(fi.contiguous(), w.contiguous(), n=ft.shape[0])  # :121-122 sims = image_feats @ text_feats.T
 
     def lens(self, model):
-        return {"vit": harness.token_lengths(_traces(model.visual.transformer.resblocks), (self.size // 16) ** 2 + 1),
+        return {"vit": harness.token_lengths(_traces(model.visual.transformer.resblocks), (self.size // self.patch) ** 2 + 1),
                 "text": harness.token_lengths(_traces(model.transformer.resblocks), self.ctx)}
 
     def flops(self, lens):
-        n0 = (self.size // 16) ** 2 + 1
+        n0 = (self.size // self.patch) ** 2 + 1
         if lens is None:
-            lens = {"vit": [n0] * 12, "text": [self.ctx] * 12}
-        return clip_tower_flops(lens["vit"], n0, 768, patch_in=768) + clip_tower_flops(lens["text"], self.ctx, 512)
+            lens = {"vit": [n0] * self.layers, "text": [self.ctx] * 12}
+        return (clip_tower_flops(lens["vit"], n0, self.width, patch_in=3 * self.patch ** 2)
+                + clip_tower_flops(lens["text"], self.ctx, self.text_width))
 
     def describe(self, B):
-        return (f"CLIP ViT-B/16 retrieval forward (encode_image + encode_text + similarity), p={self.p}, {B} image-text pairs "
+        return (f"CLIP {self.arch} retrieval forward (encode_image + encode_text + similarity), p={self.p}, {B} image-text pairs "
                 f"{self.size}x{self.size} + {self.ctx} tokens per GPU, random-init weights")
 
 

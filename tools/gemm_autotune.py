@@ -43,7 +43,11 @@ def main():
     ap.add_argument("--log", default="gpurun_out/gemm_autotune.txt")
     ap.add_argument("--quick", action="store_true", help="step 512 (smoke run of the tool)")
     ap.add_argument("--modes", default="lp,x3")
+    ap.add_argument("--classes", default=None, help="N:K:f32out,... instead of the built-in list (e.g. the ViT-L/14 classes "
+                    "3072:1024:0,1024:1024:1,4096:1024:0,1024:4096:1); write --out outside the tree for an A/B that keeps the table")
+    ap.add_argument("--mmin", type=int, default=4096)
     args = ap.parse_args()
+    classes = CLASSES if args.classes is None else [tuple(int(v) for v in c.split(":")) for c in args.classes.split(",")]
     if args.quick:
         args.step = 512
     hip.load()
@@ -54,7 +58,7 @@ def main():
     for mode in args.modes.split(","):
         x3 = mode == "x3"
         runtime.set_precision("f16x3" if x3 else "f16")
-        for N, K, f32out in CLASSES:
+        for N, K, f32out in classes:
             sel = [255] * nb
             w32 = torch.randn(N, K, device="cuda") * 0.05
             npad = (N + 127) // 128 * 128
@@ -68,7 +72,7 @@ def main():
                                    dtype=torch.float32 if f32out else (torch.float16 if x3 else torch.bfloat16))
             act = hip.ACT_GELU if N == 3072 else hip.ACT_NONE
             prev = None
-            for M in range(4096, args.mmax + 1, args.step):
+            for M in range(args.mmin, args.mmax + 1, args.step):
                 ad, out = ad_full[:M], out_full[:M]
                 kw = dict(residual=res_full[:M]) if f32out else {}
 

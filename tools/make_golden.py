@@ -609,16 +609,17 @@ def clip_block_grad_case(name, B, temperature, layer, seed=0, size=96, nsample=5
           f"{sorted(grads)} records {sorted(tap.records)}")
 
 
-def clip_vit_grad_case(name, B, temperature, seed=0, size=96, nsample=192):
+def clip_vit_grad_case(name, B, temperature, seed=0, size=96, nsample=192, patch=16, width=768, layers=12, out_dim=512):
     """SURVEY 8(f) rank 4 (backward), CLIP's vision tower end to end: the reference's OWN autograd through clip/model.py
     VisionTransformer.forward (conv1, class / positional embedding, ln_pre, twelve pruned blocks each with its own query model,
     ln_post, proj) with every parameter and space_dict as leaves, loss = sum(features * c) + sum(sd_img_ft_all * a)."""
     import clip.mock  # noqa: F401
     import clip.model as cm
     from madtp_amd import specs
-    model = cm.VisionTransformer(input_resolution=size, patch_size=16, width=768, layers=12, heads=12, output_dim=512, sd_dim=768)
+    model = cm.VisionTransformer(input_resolution=size, patch_size=patch, width=width, layers=layers, heads=width // 64,
+                                 output_dim=out_dim, sd_dim=768)
     model.eval()
-    model.load_state_dict(specs.synth_weights(specs.clip_vit_shapes("", size), seed), strict=True)
+    model.load_state_dict(specs.synth_weights(specs.clip_vit_shapes("", size, patch, width, layers, out_dim), seed), strict=True)
     images = synth.synth_images(B, size, seed)
     space_dict = synth.synth_tensor("space_dict", (100, 768), seed).clone().requires_grad_(True)
     lens, hooks = [], []
@@ -630,10 +631,11 @@ def clip_vit_grad_case(name, B, temperature, seed=0, size=96, nsample=192):
     feat, sd_all = model(images, space_dict, temperature, 1)
     for h in hooks:
         h.remove()
-    c = torch.from_numpy(synth.uniform_pm1("clipgrad_c", B * 512, seed).reshape(B, 512))
+    c = torch.from_numpy(synth.uniform_pm1("clipgrad_c", B * out_dim, seed).reshape(B, out_dim))
     a = torch.from_numpy(synth.uniform_pm1("vitgrad_a", B * 100 * 768, seed).reshape(B, 100, 768))
     ((feat * c).sum() + (sd_all * a).sum()).backward()
     rec = {"kind": "clip_vit_grad", "B": B, "size": size, "temperature": np.float64(temperature), "seed": seed, "nsample": nsample,
+           "patch": patch, "width": width, "layers": layers, "out_dim": out_dim,
            "vit_lens": np.array(lens), "features": feat.detach().numpy(), "sd_all_norm": np.float64(sd_all.detach().double().norm().item())}
     grads = {"space_dict": space_dict.grad}
     grads.update({k: v.grad for k, v in model.named_parameters() if v.grad is not None})
@@ -684,15 +686,17 @@ def clip_text_block_grad_case(name, B, N, temperature, max_keep, seed=0, nsample
     print(f"[{name}] T={temperature} in ({N},{B},512) out {tuple(y.shape)} {len(grads)} gradients")
 
 
-def clip_full_case(name, B, temperature, seed=0, size=224, min_len=6, max_len=40):
-    """clip/model.py CLIP (ViT-B/16 geometry, text width 512 / 8 heads / 12 layers / ctx 77): the reference's own
-    encode_image / encode_text (compress_retrieval_clip_dtp.py:92,100 call sites) with clip/mock.py's patched MHA."""
+def clip_full_case(name, B, temperature, seed=0, size=224, min_len=6, max_len=40, patch=16, vision_width=768, vision_layers=12,
+                   embed_dim=512, text_width=512):
+    """clip/model.py CLIP (ViT-B/16 geometry by default, text width 512 / 8 heads / 12 layers / ctx 77; ViT-L/14@336: patch 14,
+    vision width 1024 / 24 layers, embed_dim 768, text width 768 / 12 heads): the reference's own encode_image / encode_text
+    (compress_retrieval_clip_dtp.py:92,100 call sites) with clip/mock.py's patched MHA."""
     import clip.mock  # noqa: F401
     import clip.model as cm
     from madtp_amd import specs
-    model = cm.CLIP(512, size, 12, 768, 16, 77, 49408, 512, 8, 12, True, None)
+    model = cm.CLIP(embed_dim, size, vision_layers, vision_width, patch, 77, 49408, text_width, text_width // 64, 12, True, None)
     model.eval()
-    sd = specs.synth_weights(specs.clip_shapes(size), seed)
+    sd = specs.synth_weights(specs.clip_shapes(size, patch, vision_width, vision_layers, embed_dim, text_width, 12), seed)
     msg = model.load_state_dict(sd, strict=False)
     assert not msg.unexpected_keys, msg.unexpected_keys
     assert all(k.endswith("_m") or "_m." in k or "queue" in k for k in msg.missing_keys), msg.missing_keys[:8]
@@ -713,7 +717,10 @@ def clip_full_case(name, B, temperature, seed=0, size=224, min_len=6, max_len=40
         h.remove()
     tap.restore()
     rec = {"kind": "clip_full", "B": B, "size": size, "temperature": np.float64(temperature), "seed": seed,
-           "min_len": min_len, "max_len": max_len, "vit_lens": np.array(vlens), "txt_lens": np.array(tlens),
+           "min_len": min_len, "max_len": max_len, "patch": patch, "vision_width": vision_width, "vision_layers": vision_layers,
+           "embed_dim": embed_dim, "text_width": text_width,
+           "sd_img_norm": np.float64(sd_img.double().norm().item()), "sd_txt_norm": np.float64(sd_txt.double().norm().item()),
+           "vit_lens": np.array(vlens), "txt_lens": np.array(tlens),
            "image_features": img_feat.numpy(), "text_features": txt_feat.numpy(), "eot_pos": text.argmax(-1).numpy(),
            "sd_img_head": sd_img[:, :4, :16].numpy(), "sd_txt_head": sd_txt[:, :4, :16].numpy(),
            "state_dict_keys": np.array(sorted(k for k in model.state_dict().keys()))}
@@ -1307,6 +1314,8 @@ def retr_train_case(name, B, size, L, temperature, idx, alpha, queue_size, seed=
           f"losses2={rec['losses2'].round(5).tolist()} neg={rec['neg'].tolist()} {n} gradients")
 
 
+L14 = dict(patch=14, vision_width=1024, vision_layers=24, embed_dim=768, text_width=768)
+
 CASES = {
     "pos_embed_384": lambda: pos_embed_case("pos_embed_384"),
     "medopts_b2": lambda: med_layer_options_case("medopts_b2", 2, 35, 10, 30.0, pad_tail=1, Lp=20),
@@ -1346,6 +1355,11 @@ CASES = {
     "medgrad_b3_l0": lambda: med_layer_grad_case("medgrad_b3_l0", 3, 35, 30.0, layer=0, pad_tail=3),
     "medgrad_b3_l3": lambda: med_layer_grad_case("medgrad_b3_l3", 3, 35, 30.0, layer=3, pad_tail=3),
     "clipvitgrad_b2": lambda: clip_vit_grad_case("clipvitgrad_b2", 2, 4.0),
+    # ViT-L/14@336, the geometry of the reference's configs/retrieval_{coco,flickr}_clip.yaml (clip_large_retrieval_*.pth)
+    "clipl14_full_b2_T4": lambda: clip_full_case("clipl14_full_b2_T4", 2, 4.0, size=336, **L14),
+    "clipl14_full_b2_T40": lambda: clip_full_case("clipl14_full_b2_T40", 2, 40.0, seed=1, size=336, **L14),
+    "clipl14vitgrad_b2": lambda: clip_vit_grad_case("clipl14vitgrad_b2", 2, 4.0, size=112, patch=14, width=1024, layers=24,
+                                                    out_dim=768),
     "cliptextgrad_b2": lambda: clip_text_block_grad_case("cliptextgrad_b2", 2, 24, 3.0, 4),
     "clipgrad_b2_l1": lambda: clip_block_grad_case("clipgrad_b2_l1", 2, 4.0, layer=1),
     "trainstep_cap_b2": lambda: cap_train_case("trainstep_cap_b2", 2, 96, 12, 20.0),
