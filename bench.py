@@ -2,7 +2,11 @@
 """Headline benchmark: images/sec of the pruned BLIP-base NLVR2 forward (BLIP_NLVR.forward(train=False) dataflow,
 reference models/blip_nlvr.py:63-100) at p=0.5, 64 samples (= 128 images) per GPU, bf16 GEMM operands, on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W --precision bf16|f16x3|fp32 --config nlvr|retrieval|clip|vqa --batch B]
+    python bench.py [--gpus N --steps K --warmup W --precision bf16|f16x3|fp32 --config nlvr|retrieval|clip|vqa --batch B] [--full]
+
+A plain run does what the headline figure needs and nothing else: it sets up, warms up, times the K steps, writes the outputs
+of --dump-outputs and prints the line.  --full adds every other leg described below (serial loop, roofline with its counter
+passes, parity_mode and the other fast mode, index_match, cpu_baseline); it never changes the timed K steps.
 
 --config selects one of BASELINE.json's GPU configurations (madtp_amd/workloads.py); the default is the one the metric is
 quoted on (config 2, NLVR2 b64).  N>1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N ...
@@ -11,15 +15,16 @@ pair stay on one rank), weights replicated, NO collective inside the forward (th
 8(e)); RCCL is used only for the barrier and the MAX-reduction of the elapsed time.  Scaling is "weak" (retrieval, whose
 BASELINE batch of 128 is a global one, is split over the ranks: "strong").
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...); with --full it carries extra objects:
+  single_stream / serial_value - the same K forwards once more, one after the other on one stream (runs with forwards in flight).
   roofline     - the dominant kernel (the MFMA GEMM): algorithmic FLOPs of its launches in the timed region / the sum of their
                  durations, measured live with HIP events on the launch stream; `traffic` = HBM bytes per launch from two
                  rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) that THIS run starts on a 1-step copy of itself; `mfma_busy` /
                  `sq_counters` from a third pass (SQ_VALU_MFMA_BUSY_CYCLES, wave-cycle split; counters for the GEMM kernels only);
                  `by_class` = every Linear class against its own bound (MFMA or HBM) with its tile-quantisation ceiling.
-  value        - the bf16 leg (BASELINE.json config 2's dtype); f16_value = the same runner on IEEE f16 operands;
-                 parity_qualified_value = the f16x3 leg (every kept set identical to the oracle).  The timed region is exactly
-                 the K = --steps forwards after the warm-up; ms_per_step = its wall time / K.
+  f16_value    - the same runner on IEEE f16 operands (`value` itself is the bf16 leg, BASELINE.json config 2's dtype);
+                 parity_qualified_value = the f16x3 leg (every kept set identical to the oracle).  In every run the timed region
+                 is exactly the K = --steps forwards after the warm-up; ms_per_step = its wall time / K.
   parity_mode  - the same workload timed in the precision mode that carries the parity claim ("f16x3": fp32-accurate GEMMs
                  on the f16 MFMA) + index_match of every mode vs the CPU oracle at the headline batch.
   cpu_baseline - oracle/ (the CPU restatement of the reference forward, kind "port") timed on this box's host cores on a
@@ -194,8 +199,8 @@ def measure_traffic(args):
             # on the same box, interleaved (tools/pmc_hang_probe.sh, profiles/r06_pmc_hang_probe.txt), and a pass takes 4 s instead of 6.
             cmd = [exe, "--pmc"] + pmc + ["--kernel-trace", "--kernel-include-regex", "gemm_(ws|pp|sq)_kernel", "-d", d, "-o", "p", "--",
                    sys.executable, os.path.abspath(__file__),
-                   "--config", args.config, "--precision", args.precision, "--steps", "1", "--warmup", "1", "--traffic", "off", "--min-seconds", "0",
-                   "--no-cpu-baseline", "--no-parity", "--no-bf16-leg", "--no-gemm-events", "--inflight", "1"] + (["--batch", str(args.batch)] if args.batch else [])
+                   "--config", args.config, "--precision", args.precision, "--steps", "1", "--warmup", "1", "--min-seconds", "0",
+                   "--inflight", "1"] + (["--batch", str(args.batch)] if args.batch else [])  # (no --full: the headline leg only)
             env = dict(os.environ, TMPDIR="/tmp")
             # Every pass gets a bounded time, the three passes together at most MADTP_TRAFFIC_BUDGET seconds (a pass normally takes
             # 12-15 s).  A pass is never started again: a profiled child that hung or died of a signal (GPU fault, abort,
@@ -282,7 +287,17 @@ def main():
     ap.add_argument("--inflight", type=int, default=int(os.environ.get("MADTP_INFLIGHT", "0")),
                     help="forwards in flight per GPU (madtp_amd.pipeline: one host thread + HIP stream + model replica each; "
                          "1 = the serial loop, 0 = the configuration's default).  The K timed steps are K whole forwards either way.")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg besides the headline: the serial loop, the roofline leg with its counter passes, the parity_mode "
+                         "and other-fast-mode legs, index_match and cpu_baseline (the --no-* switches and --traffic off still leave one "
+                         "out).  Without it a run times the K steps and prints the line, nothing more")
     args = ap.parse_args()
+    # The in-flight runner is sized as for a --full run in every run (slots for the parity_mode leg unless --no-parity), so that
+    # the timed steps run on the same workers, inputs and CU split with and without --full.
+    parity_slots = not args.no_parity
+    if not args.full:
+        args.no_parity = args.no_cpu_baseline = args.no_gemm_events = args.no_bf16_leg = True
+        args.traffic = "off"
     if os.environ.get("MADTP_BENCH_WATCHDOG"):  # debugging aid: dump every thread's Python stack after N seconds (tools/pmc_hang_probe.sh)
         import faulthandler
         faulthandler.dump_traceback_later(float(os.environ["MADTP_BENCH_WATCHDOG"]), repeat=False, file=sys.stderr)
@@ -345,7 +360,7 @@ def main():
         from madtp_amd.pipeline import InflightRunner
         # one runner for both legs: the headline uses the first args.inflight workers, the parity_mode leg args.parity_inflight
         from madtp_amd.pipeline import partition_from_env
-        n_slots = args.inflight if args.no_parity else max(args.inflight, args.parity_inflight)
+        n_slots = max(args.inflight, args.parity_inflight) if parity_slots else args.inflight
         if args.partition:
             os.environ["MADTP_INFLIGHT_CUMASK"] = args.partition
         part = partition_from_env(n_slots, getattr(w, "default_partition", None))
@@ -372,13 +387,14 @@ def main():
         if runner is not None:
             runner.run(max(args.warmup, 3) * args.inflight, workers=args.inflight)  # every replica prepares its weights, grows its workspace and its
             #                                                  stream's allocator pool (>= 3 forwards per worker)
-            # the serial loop of the same K steps, for the record (latency of one forward; rounds 1-2 reported this as `value`)
-            torch.cuda.synchronize()
-            ts = time.perf_counter()
-            for _ in range(args.steps):
-                step()
-            torch.cuda.synchronize()
-            single = time.perf_counter() - ts
+            if args.full:
+                # the serial loop of the same K steps, for the record (latency of one forward; rounds 1-2 reported this as `value`)
+                torch.cuda.synchronize()
+                ts = time.perf_counter()
+                for _ in range(args.steps):
+                    step()
+                torch.cuda.synchronize()
+                single = time.perf_counter() - ts
         torch.cuda.synchronize()
         repeats = 1
         if args.min_seconds > 0:
@@ -490,10 +506,12 @@ def main():
     }
     # First-class companions of `value`: `value` is THROUGHPUT with args.inflight independent forwards in flight on one
     # GPU (args.inflight model replicas); the reference's eval loop runs one batch at a time (compress_nlvr_dtp.py:73-99), which is
-    # `serial_value` / `ms_per_forward` here.  ms_per_step = elapsed / steps is the pipeline's issue interval, not a latency.
-    if single is not None:
-        out["serial_value"] = round(w.images_per_sample * B * world * args.steps / single, 1)
-        out["ms_per_forward"] = round(1e3 * single / args.steps, 3)
+    # `serial_value` / `ms_per_forward` here (timed by --full only when forwards are in flight).  ms_per_step = elapsed / steps is the
+    # pipeline's issue interval, not a latency.
+    if runner is not None:
+        if single is not None:
+            out["serial_value"] = round(w.images_per_sample * B * world * args.steps / single, 1)
+            out["ms_per_forward"] = round(1e3 * single / args.steps, 3)
         out["ms_per_forward_in_flight"] = round(1e3 * elapsed * args.inflight / args.steps, 3)
     else:
         out["serial_value"] = out["value"]

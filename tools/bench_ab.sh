@@ -5,7 +5,7 @@ OUT=$1; ROUNDS=$2; shift 2
 for r in $(seq 1 $ROUNDS); do
   for spec in "$@"; do
     NAME=${spec%%:*}; ENVS=${spec#*:}
-    LINE=$(env $ENVS python bench.py --no-parity --no-cpu-baseline --traffic off ${BENCH_ARGS:-} 2>/dev/null | tail -1)
+    LINE=$(env $ENVS python bench.py --full --no-parity --no-cpu-baseline --traffic off ${BENCH_ARGS:-} 2>/dev/null | tail -1)
     python - "$NAME" "$r" "$LINE" >> $OUT <<'PY'
 import json, sys
 name, r, line = sys.argv[1:4]

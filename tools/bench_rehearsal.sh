@@ -10,7 +10,7 @@ N=${1:-2}; shift
 CONFIGS=${@:-nlvr retrieval}
 mkdir -p gpurun_out
 for C in $CONFIGS; do
-  timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29571 bench.py --gpus $N \
+  timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29571 bench.py --gpus $N --full \
       --config $C --steps 8 --warmup 2 --parity-steps 8 --bf16-steps 8 2>gpurun_out/rehearsal_${C}_n$N.err | tail -1 > gpurun_out/rehearsal_${C}_n$N.json
   python - <<PY
 import json

@@ -8,7 +8,7 @@ mkdir -p "$(dirname "$OUT")"
 run() {  # label, inflight, partition, extra env
   local label=$1 nf=$2 part=$3; shift 3
   local line
-  line=$(env "$@" MADTP_INFLIGHT_CUMASK="$part" python bench.py --precision "$PREC" --steps "$STEPS" --warmup 3 --inflight "$nf" \
+  line=$(env "$@" MADTP_INFLIGHT_CUMASK="$part" python bench.py --precision "$PREC" --steps "$STEPS" --warmup 3 --inflight "$nf" --full \
          --no-parity --no-cpu-baseline --no-gemm-events --traffic off 2>/dev/null | tail -1)
   python - "$label" "$line" >> "$OUT" <<'PY'
 import json, sys
