@@ -63,8 +63,7 @@ struct AttnArgs {
 struct HmWorkspace { unsigned* ws; int* tick; };
 constexpr int HM_MAX_WGS = 384, HM_MAX_NT = 40, HM_MAX_GZ = 4;  // (attn_bf16_large_kernel splits the heads over up to 4 workgroups)
 static bool hm_workspace(hipStream_t s, HmWorkspace& out) {
-    static int env = -1;
-    if (env < 0) { const char* e = getenv("MADTP_ATTN_HEAD_SPLIT"); env = e ? atoi(e) : 1; }
+    static const int env = env_int("MADTP_ATTN_HEAD_SPLIT", 1);
     if (!env) return false;
     static std::mutex mu;
     static std::map<std::pair<int, hipStream_t>, HmWorkspace> pool;
@@ -2053,8 +2052,7 @@ int launch_attn_bf16_large(const AttnArgs& a_in, hipStream_t s) {
     int gz = 1;
     if constexpr (SCORES && NCH == 8) {
         // 641..1024 keys with scores: the three-sweep order (HV = 2), two workgroups per CU (MADTP_ATTN_HV=0: the one-sweep order)
-        static int hv_env = -1;
-        if (hv_env < 0) { const char* e = getenv("MADTP_ATTN_HV"); hv_env = e ? atoi(e) : 1; }
+        static const int hv_env = env_int("MADTP_ATTN_HV", 1);
         if (hv_env && a.H <= 16 && (a.Nk + 127) / 128 > NCH / 2) {
             float* op = opart_workspace(s, (size_t)a.B * a.Nq * a.H * 64 * sizeof(float));
             if (op) {
@@ -2086,8 +2084,7 @@ int launch_attn_bf16_large(const AttnArgs& a_in, hipStream_t s) {
                 const int cost = ((wgs * z + cap - 1) / cap) * (a.H / z);
                 if (cost < best_cost) { best_cost = cost; best = z; }
             }
-            static int gz_env = -1;  // MADTP_ATTN_HEAD_GROUPS=2..4 forces the split (A/B runs)
-            if (gz_env < 0) { const char* e = getenv("MADTP_ATTN_HEAD_GROUPS"); gz_env = e ? atoi(e) : 0; }
+            static const int gz_env = env_int("MADTP_ATTN_HEAD_GROUPS", 0);  // 2..4 forces the split (A/B runs)
             if (gz_env >= 2 && gz_env <= HM_MAX_GZ && a.H % gz_env == 0) best = gz_env;
             gz = best; a.hm_ws = hw.ws; a.hm_tick = hw.tick;
         }
@@ -2199,77 +2196,69 @@ extern "C" int madtp_attention(const void* q, const void* k, const void* v, void
                                    scale, io_dtype, stream);
 }
 
-static int attention_launch(const void* q, const void* k, const void* v, const int32_t* kv_batch_index, void* out,
-                            const float* add_mask, const float* mask_qk, int ld_mask_qk, float* colsum_part, float* p0,
-                            float* onorm, int B, int H, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, float scale,
-                            int io_dtype, void* stream, const int32_t* n_dev = nullptr, int dev_q_only = 0, int kv_block_rows = 0);
-
 int madtp_i_attention(const void* q, const void* k, const void* v, void* out, float* colsum_part, float* p0, float* onorm, int B,
                       int H, int N, int ldq, int ldk, int ldv, int ldo, float scale, int io_dtype, const int32_t* n_dev,
                       void* stream) {
     if (N > 256) return MADTP_E_SHAPE;  // the two-pass long-sequence kernels keep host-side lengths
-    return attention_launch(q, k, v, nullptr, out, nullptr, nullptr, 0, colsum_part, p0, onorm, B, H, N, N, ldq, ldk, ldv, ldo, scale,
-                            io_dtype, stream, n_dev);
+    return madtp_i_attention_launch(q, k, v, nullptr, out, nullptr, nullptr, 0, colsum_part, p0, onorm, B, H, N, N, ldq, ldk, ldv, ldo, scale,
+                                    io_dtype, 0, stream, n_dev);
 }
 // the same with an additive key mask [B, n] (rows of the DEVICE length: the text encoders' compacted padding mask)
 int madtp_i_attention_mask(const void* q, const void* k, const void* v, void* out, const float* add_mask, float* colsum_part, float* p0,
                            float* onorm, int B, int H, int N, int ldq, int ldk, int ldv, int ldo, float scale, int io_dtype,
                            const int32_t* n_dev, void* stream) {
     if (N > 256) return MADTP_E_SHAPE;
-    return attention_launch(q, k, v, nullptr, out, add_mask, nullptr, 0, colsum_part, p0, onorm, B, H, N, N, ldq, ldk, ldv, ldo, scale,
-                            io_dtype, stream, n_dev);
+    return madtp_i_attention_launch(q, k, v, nullptr, out, add_mask, nullptr, 0, colsum_part, p0, onorm, B, H, N, N, ldq, ldk, ldv, ldo, scale,
+                                    io_dtype, 0, stream, n_dev);
 }
 // attention of Nq queries per sample against the first Nk rows of that sample's K/V BLOCK of kv_block_rows rows (the decoder's
 // self-attention cache [rows, Lmax, 2 dim]: incremental decoding, models/med.py:1071-1094); no scores, <= 256 keys
 int madtp_i_attention_cached(const void* q, const void* k, const void* v, int kv_block_rows, void* out, int B, int H, int Nq, int Nk,
                              int ldq, int ldk, int ldv, int ldo, float scale, int io_dtype, void* stream) {
-    return attention_launch(q, k, v, nullptr, out, nullptr, nullptr, 0, nullptr, nullptr, nullptr, B, H, Nq, Nk, ldq, ldk, ldv, ldo, scale,
-                            io_dtype, stream, nullptr, 0, kv_block_rows);
+    return madtp_i_attention_launch(q, k, v, nullptr, out, nullptr, nullptr, 0, nullptr, nullptr, nullptr, B, H, Nq, Nk, ldq, ldk, ldv, ldo, scale,
+                                    io_dtype, 0, stream, nullptr, 0, kv_block_rows);
 }
 // cross-attention with *nq_dev query tokens per sample against Nk (host-side) keys of another sequence, optional K/V batch index
 int madtp_i_attention_cross(const void* q, const void* k, const void* v, const int32_t* kv_batch_index, void* out, const float* add_mask,
                             int B, int H, int Nq_max, int Nk, int ldq, int ldk, int ldv, int ldo, float scale, int io_dtype,
                             const int32_t* nq_dev, void* stream) {
     if (Nk > 256 || Nq_max > 256) return MADTP_E_SHAPE;
-    return attention_launch(q, k, v, kv_batch_index, out, add_mask, nullptr, 0, nullptr, nullptr, nullptr, B, H, Nq_max, Nk, ldq, ldk,
-                            ldv, ldo, scale, io_dtype, stream, nq_dev, 1);
+    return madtp_i_attention_launch(q, k, v, kv_batch_index, out, add_mask, nullptr, 0, nullptr, nullptr, nullptr, B, H, Nq_max, Nk, ldq, ldk,
+                                    ldv, ldo, scale, io_dtype, 0, stream, nq_dev, 1);
 }
 
 extern "C" int madtp_attention_indexed(const void* q, const void* k, const void* v, const int32_t* kv_batch_index, void* out,
                                        const float* add_mask, float* colsum_part, float* p0, float* onorm, int B, int H,
                                        int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, float scale, int io_dtype,
                                        void* stream) {
-    return attention_launch(q, k, v, kv_batch_index, out, add_mask, nullptr, 0, colsum_part, p0, onorm, B, H, Nq, Nk, ldq, ldk,
-                            ldv, ldo, scale, io_dtype, stream);
+    return madtp_i_attention_launch(q, k, v, kv_batch_index, out, add_mask, nullptr, 0, colsum_part, p0, onorm, B, H, Nq, Nk, ldq, ldk,
+                                    ldv, ldo, scale, io_dtype, 0, stream);
 }
 
 extern "C" int madtp_attention_qk_mask(const void* q, const void* k, const void* v, void* out, const float* add_mask,
                                        const float* mask_qk, int ld_mask_qk, float* colsum_part, float* p0, float* onorm, int B,
                                        int H, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, float scale, int io_dtype,
                                        void* stream) {
-    if (mask_qk && (ld_mask_qk < Nk || Nk > 256)) return MADTP_E_SHAPE;  // the <= 256-key kernels carry the [Nq,Nk] mask
-    return attention_launch(q, k, v, nullptr, out, add_mask, mask_qk, ld_mask_qk, colsum_part, p0, onorm, B, H, Nq, Nk, ldq, ldk,
-                            ldv, ldo, scale, io_dtype, stream);
+    return madtp_i_attention_launch(q, k, v, nullptr, out, add_mask, mask_qk, ld_mask_qk, colsum_part, p0, onorm, B, H, Nq, Nk, ldq, ldk,
+                                    ldv, ldo, scale, io_dtype, 0, stream);
 }
 
-// Split-plane output request of the f16x3 layer calls (layers.hip): the NEXT attention launches of this thread with io_dtype
-// MADTP_F16S write their context as f16-split planes (AttnArgs.split_dim; `out` = f16 planes, ldo in f16 elements) when they run on
-// an f16s kernel, and say so through madtp_internal_attn_split_done() - a launch that falls back to another kernel writes f32 as
-// before is impossible with a planes buffer, so the request is only made where the caller checked the same conditions.
-static thread_local int t_split_dim = 0, t_split_done = 0;
-int madtp_internal_attn_split_out(int split_dim) { t_split_dim = split_dim > 0 ? split_dim : 0; t_split_done = 0; return 0; }
-int madtp_internal_attn_split_done() { return t_split_done; }
 bool madtp_internal_attn_f16s_enabled() {
-    static int f16s_env = -1;  // MADTP_ATTN_F16S=0: the f16x3 mode keeps its attention on the exact-f32 MFMA kernels (A/B runs)
-    if (f16s_env < 0) { const char* e = getenv("MADTP_ATTN_F16S"); f16s_env = e ? atoi(e) : 1; }
+    static const int f16s_env = env_int("MADTP_ATTN_F16S", 1);  // 0: the f16x3 mode keeps its attention on the exact-f32 MFMA kernels (A/B runs)
     return f16s_env != 0;
 }
 
-static int attention_launch(const void* q, const void* k, const void* v, const int32_t* kv_batch_index, void* out,
-                            const float* add_mask, const float* mask_qk, int ld_mask_qk, float* colsum_part, float* p0,
-                            float* onorm, int B, int H, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, float scale,
-                            int io_dtype, void* stream, const int32_t* n_dev, int dev_q_only, int kv_block_rows) {
+// The launcher behind every attention entry point.  split_req > 0 is the split-plane output request of the f16x3 layer calls
+// (layers.hip): a launch with io_dtype MADTP_F16S writes its context as f16-split planes (AttnArgs.split_dim; `out` = f16 planes,
+// ldo in f16 elements, P1 at column offset split_req).  A fall-back to a kernel that writes f32 is impossible with a planes buffer,
+// so the request is an error unless the f16s kernels are on (the callers check madtp_internal_attn_f16s_enabled()).
+int madtp_i_attention_launch(const void* q, const void* k, const void* v, const int32_t* kv_batch_index, void* out,
+                             const float* add_mask, const float* mask_qk, int ld_mask_qk, float* colsum_part, float* p0,
+                             float* onorm, int B, int H, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, float scale,
+                             int io_dtype, int split_req, void* stream, const int32_t* n_dev, int dev_q_only, int kv_block_rows) {
     if (!q || !k || !v || !out || B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0) return MADTP_E_BADARG;
+    if (mask_qk && (ld_mask_qk < Nk || Nk > 256)) return MADTP_E_SHAPE;  // the <= 256-key kernels carry the [Nq,Nk] mask
+    if (split_req < 0) split_req = 0;
     if (kv_block_rows && (kv_block_rows < Nk || Nk > 256 || colsum_part)) return MADTP_E_SHAPE;  // (the <= 256-key kernels without scores)
     if (kv_batch_index && colsum_part) return MADTP_E_BADARG;  // indexed K/V is a cross-attention feature
     // io_dtype MADTP_F16S: f32 storage, products as three f16 MFMA products of f16-split operands (the f16x3 precision mode)
@@ -2280,9 +2269,9 @@ static int attention_launch(const void* q, const void* k, const void* v, const i
     if (f16s) {
         f16s = madtp_internal_attn_f16s_enabled();
         io_dtype = MADTP_F32;
-        split_dim = f16s ? t_split_dim : 0;
-        if (t_split_dim && !f16s) return MADTP_E_BADARG;  // (the caller asks for planes only when the f16s kernels are on)
-    } else if (t_split_dim) {
+        split_dim = f16s ? split_req : 0;
+        if (split_req && !f16s) return MADTP_E_BADARG;  // (the caller asks for planes only when the f16s kernels are on)
+    } else if (split_req) {
         return MADTP_E_BADARG;
     }
     if (colsum_part && (!p0 || !onorm || Nq != Nk)) return MADTP_E_BADARG;
@@ -2306,7 +2295,6 @@ static int attention_launch(const void* q, const void* k, const void* v, const i
     const bool scores = colsum_part != nullptr;
     if (split_dim) {  // planes: 8-byte stores at f16 offsets
         if ((ldo % 4) || (split_dim % 4) || ((uintptr_t)out & 7)) return MADTP_E_ALIGN;
-        t_split_done = 1;
         if (Nk > 256) return scores ? dispatch_large_f16s<true>(a, s) : dispatch_large_f16s<false>(a, s);
         return scores ? dispatch_nt_f16s<true>(a, s) : dispatch_nt_f16s<false>(a, s);
     }
@@ -2314,8 +2302,7 @@ static int attention_launch(const void* q, const void* k, const void* v, const i
         if (f16s && (ldo * 4) % 16 == 0 && aligned16(out))
             return scores ? dispatch_large_f16s<true>(a, s) : dispatch_large_f16s<false>(a, s);
         if (io_dtype == MADTP_F32) return scores ? dispatch_large<float, true>(a, s) : dispatch_large<float, false>(a, s);
-        static int large_env = -1;  // MADTP_ATTN_LARGE_F32=1: bf16 storage on the exact-f32 MFMA kernel (A/B runs)
-        if (large_env < 0) { const char* e = getenv("MADTP_ATTN_LARGE_F32"); large_env = e ? atoi(e) : 0; }
+        static const int large_env = env_int("MADTP_ATTN_LARGE_F32", 0);  // 1: bf16 storage on the exact-f32 MFMA kernel (A/B runs)
         if (f16) return scores ? dispatch_bf16_large<true, true>(a, s) : dispatch_bf16_large<false, true>(a, s);
         if (large_env) return scores ? dispatch_large<bf16_t, true>(a, s) : dispatch_large<bf16_t, false>(a, s);
         return scores ? dispatch_bf16_large<true>(a, s) : dispatch_bf16_large<false>(a, s);  // fast mode: bf16 MFMA, LDS-DMA ring
@@ -2342,27 +2329,27 @@ extern "C" int madtp_attention_pair(const void* q0, const void* q1, const void* 
                                     const float* add_mask1, int B, int H, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo,
                                     float scale, int io_dtype, void* stream) {
     return madtp_i_attention_pair(q0, q1, k0, k1, v0, v1, kv_batch_index, out0, out1, add_mask0, add_mask1, B, H, Nq, Nk, ldq, ldk, ldv,
-                                  ldo, scale, io_dtype, nullptr, stream);
+                                  ldo, scale, io_dtype, 0, nullptr, stream);
 }
 // nq_dev != NULL: the sync-free text encoder - *nq_dev query tokens per sample (Nq is the worst case), <= 256 keys
 int madtp_i_attention_pair(const void* q0, const void* q1, const void* k0, const void* k1, const void* v0, const void* v1,
                            const int32_t* kv_batch_index, void* out0, void* out1, const float* add_mask0, const float* add_mask1, int B,
-                           int H, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, float scale, int io_dtype, const int32_t* nq_dev,
-                           void* stream) {
+                           int H, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, float scale, int io_dtype, int split_dim,
+                           const int32_t* nq_dev, void* stream) {
     if (nq_dev && (Nk > 256 || Nq > 256)) return MADTP_E_SHAPE;
     if (!q0 || !q1 || !k0 || !k1 || !v0 || !v1 || !out0 || !out1 || B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0) return MADTP_E_BADARG;
-    static int pair_env = -1;  // MADTP_ATTN_PAIR=0: always two launches (A/B runs)
-    if (pair_env < 0) { const char* e = getenv("MADTP_ATTN_PAIR"); pair_env = e ? atoi(e) : 1; }
+    static const int pair_env = env_int("MADTP_ATTN_PAIR", 1);  // 0: always two launches (A/B runs)
     const bool one = pair_env && (io_dtype == MADTP_BF16 || io_dtype == MADTP_F16) && Nk <= 256 && (!add_mask0) == (!add_mask1) && aligned16(q0) &&
                      aligned16(q1) && aligned16(k0) && aligned16(k1) && aligned16(v0) && aligned16(v1) && (ldq * 2) % 16 == 0 &&
                      (ldk * 2) % 16 == 0 && (ldv * 2) % 16 == 0;
     if (!one) {
-        const int rc = attention_launch(q0, k0, v0, kv_batch_index, out0, add_mask0, nullptr, 0, nullptr, nullptr, nullptr, B, H, Nq, Nk,
-                                        ldq, ldk, ldv, ldo, scale, io_dtype, stream, nq_dev, nq_dev ? 1 : 0);
+        const int rc = madtp_i_attention_launch(q0, k0, v0, kv_batch_index, out0, add_mask0, nullptr, 0, nullptr, nullptr, nullptr, B, H, Nq, Nk,
+                                                ldq, ldk, ldv, ldo, scale, io_dtype, split_dim, stream, nq_dev, nq_dev ? 1 : 0);
         if (rc) return rc;
-        return attention_launch(q1, k1, v1, kv_batch_index, out1, add_mask1, nullptr, 0, nullptr, nullptr, nullptr, B, H, Nq, Nk, ldq, ldk,
-                                ldv, ldo, scale, io_dtype, stream, nq_dev, nq_dev ? 1 : 0);
+        return madtp_i_attention_launch(q1, k1, v1, kv_batch_index, out1, add_mask1, nullptr, 0, nullptr, nullptr, nullptr, B, H, Nq, Nk, ldq,
+                                        ldk, ldv, ldo, scale, io_dtype, split_dim, stream, nq_dev, nq_dev ? 1 : 0);
     }
+    if (split_dim) return MADTP_E_BADARG;  // the one-launch branch (bf16 / f16 storage) writes no planes
     AttnArgs a;
     a.q = (const char*)q0; a.k = (const char*)k0; a.v = (const char*)v0; a.out = (char*)out0; a.mask = add_mask0;
     a.q2 = (const char*)q1; a.k2 = (const char*)k1; a.v2 = (const char*)v1; a.out2 = (char*)out1; a.mask2 = add_mask1;

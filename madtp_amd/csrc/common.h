@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <atomic>
 
 #include "../../include/madtp_hip.h"
@@ -227,6 +228,10 @@ constexpr int DIMS_STRIDE = 4;
     } while (0)
 
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+
+// An integer environment switch.  Read it as `static const int v = env_int(...)`: the initialisation of a function-local static
+// is thread-safe, so launches from several host threads (madtp_amd/pipeline.py) do not race on the first read.
+static inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
 
 // ---- LayerNorm of one row held by one wave (shared by norm.hip and the gather+LayerNorm fusion in prune.hip) ----
 constexpr int LN_MAX_CHUNKS = 4;  // dim <= 1024

@@ -302,10 +302,9 @@ __device__ __forceinline__ long long ws_now() {
 }
 #define WS_NOW() ws_now()
 #endif
-template <bool X3, int OM, bool M32 = false, bool F16 = false>
+template <bool X3, int OM, bool F16 = false>
 __global__ __launch_bounds__(768, 1) void gemm_ws_kernel(GemmArgs g) {
-    static_assert(!(X3 && M32), "the 32x32x16 consumer loop exists for the bf16 kernel only");
-    static_assert(!(F16 && (X3 || M32)), "plain f16 operands run the 16x16x32 consumer loop");
+    static_assert(!(F16 && X3), "plain f16 operands are not split into planes");
     constexpr bool MF16 = X3 || F16;  // which 16x16x32 MFMA: f16 (split planes or plain f16 operands) or bf16
     constexpr bool LP_OUT = OM != OM_F32;
     constexpr int ESZ = 2, BM = 256, BN = 128, STAGES = 3, NCW = 8, NLW = 4;
@@ -365,7 +364,7 @@ __global__ __launch_bounds__(768, 1) void gemm_ws_kernel(GemmArgs g) {
                 const int idx = lw * PER + q;                     // 8-row group of the stage image: A groups, then W groups
                 const bool is_a = idx < BM / 8;
                 const int r = (is_a ? idx : idx - BM / 8) * 8 + sub;  // row within the A / W tile
-                const int key = M32 ? swz_key32(r) : (is_a ? (r & 7) : swz_key<LP_OUT>(r));
+                const int key = is_a ? (r & 7) : swz_key<LP_OUT>(r);
                 int row = (is_a ? im0 : in0) + r;
                 const int lim = is_a ? g.M - 1 : n_pad_max;
                 row = row < lim ? row : lim;
@@ -413,98 +412,6 @@ __global__ __launch_bounds__(768, 1) void gemm_ws_kernel(GemmArgs g) {
 
     // ------------------------------------------ consumer ------------------------------------------
     const int grp = wave >> 2, wr = (wave >> 1) & 1, wc = wave & 1;
-    if constexpr (M32) {
-        // 32x32x16 consumer loop: the wave's 64x64 block is 2x2 fragments of 32x32 (4 x 16 accumulators); a 64-deep slab is
-        // four 16-deep k-steps, read as two halves X (k-steps 0, 1) and Y (2, 3) of 4 A + 4 W fragments each - the same 16
-        // ds_read_b128 per slab as the 16x16x32 loop, half a slab ahead of the MFMAs that use them, but 16 MFMA issues per
-        // slab instead of 32.  No stream-K tail on this variant (g.sk == 0).
-        const int l32 = lane & 31, h = lane >> 5;
-        const int a_rd = (grp * 128 + wr * 64 + l32) * ROWB, a_k = swz_key32(l32);
-        const int rw = wc * 64 + wfrag_row32<LP_OUT>(0, l32);
-        const int w_rd = A_BYTES + rw * ROWB, w_k = swz_key32(rw);
-        f32x16 acc[2][2];
-        bf16x8 xa[4], xb[4], ya[4], yb[4];
-        int cur_stage = 0;
-#define WS32_READ(XA, XB, CH)                                                                      \
-    if (!(MADTP_WS_ABLATE & 1) || first)                                                           \
-    _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                               \
-        _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                            \
-            XA[ks * 2 + i] = *(const bf16x8*)(st + a_rd + i * 32 * ROWB + ((((CH) + 2 * ks + h) ^ a_k) << 4)); \
-            XB[ks * 2 + i] = *(const bf16x8*)(st + w_rd + i * 32 * ROWB + ((((CH) + 2 * ks + h) ^ w_k) << 4)); \
-        }
-#define WS32_MFMA(XA, XB)                                                                          \
-    if (!(MADTP_WS_ABLATE & 4))                                                                    \
-    _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                               \
-        _Pragma("unroll") for (int i = 0; i < 2; ++i)                                              \
-            _Pragma("unroll") for (int j = 0; j < 2; ++j)                                          \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(XB[ks * 2 + j], XA[ks * 2 + i], acc[i][j], 0, 0, 0);
-        for (int unit = 0; unit < n_units; ++unit) {
-            const int slot = lb + unit * gl;
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int t = 0; t < 16; ++t) acc[i][j][t] = 0.f;
-            {
-                constexpr bool first = true;
-                const char* st = smem + cur_stage * STAGE_BYTES;
-                if (!(MADTP_WS_ABLATE & 2)) __builtin_amdgcn_s_barrier();
-                WS32_READ(xa, xb, 0)
-                WS32_READ(ya, yb, 4)
-                __builtin_amdgcn_sched_barrier(0);
-                WS32_MFMA(xa, xb)
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_waitcnt(0xC07F);
-                __builtin_amdgcn_sched_barrier(0);
-                if (++cur_stage == STAGES) cur_stage = 0;
-            }
-            for (int kt = 1; kt < nk; ++kt) {
-                constexpr bool first = false;
-                const char* st = smem + cur_stage * STAGE_BYTES;
-                if (!(MADTP_WS_ABLATE & 2)) __builtin_amdgcn_s_barrier();
-                WS32_READ(xa, xb, 0)
-                __builtin_amdgcn_sched_barrier(0);
-                WS32_MFMA(ya, yb)
-                __builtin_amdgcn_sched_barrier(0);
-                WS32_READ(ya, yb, 4)
-                __builtin_amdgcn_sched_barrier(0);
-                WS32_MFMA(xa, xb)
-                __builtin_amdgcn_sched_barrier(0);
-                __builtin_amdgcn_s_waitcnt(0xC07F);
-                __builtin_amdgcn_sched_barrier(0);
-                if (++cur_stage == STAGES) cur_stage = 0;
-            }
-            { WS32_MFMA(ya, yb) }
-            int t = t0 + slot;
-            const bool second = g.pair && t >= tiles1;
-            if (second) t -= tiles1;
-            int ctm, ctn;
-            tile_mn(g, t, ctm, ctn);
-            const int row_t = ctm * BM + grp * 128 + wr * 64, col_w = ctn * BN + wc * 64;
-            if (!((g.dbg & 1) && acc[0][0][0] != 12345.678f)) {
-                GemmArgs ge = g;
-                if (second) { ge.bias = g.bias2; ge.C = g.C2; ge.acc_scale = g.acc_scale2; }
-#define EPI(ACT)                                                                                   \
-    if constexpr (LP_OUT) {                                                                        \
-        epilogue32<OM, ACT, false>(ge, acc, row_t, col_w, l32, h);                                  \
-    } else {                                                                                       \
-        if (g.residual) epilogue32<OM, ACT, true>(ge, acc, row_t, col_w, l32, h);                   \
-        else epilogue32<OM, ACT, false>(ge, acc, row_t, col_w, l32, h);                             \
-    }
-                switch (g.act) {
-                    case MADTP_ACT_GELU_ERF: EPI(MADTP_ACT_GELU_ERF) break;
-                    case MADTP_ACT_QUICK_GELU: EPI(MADTP_ACT_QUICK_GELU) break;
-                    case MADTP_ACT_RELU: EPI(MADTP_ACT_RELU) break;
-                    default: EPI(MADTP_ACT_NONE) break;
-                }
-#undef EPI
-            }
-        }
-#undef WS32_READ
-#undef WS32_MFMA
-        return;
-    }
     const int l16 = lane & 15, grp4 = lane >> 4;
     f32x4 acc[4][4];
     int a_off[4], a_key[4], b_off[4], b_key[4];
@@ -970,9 +877,6 @@ static int gemm_launch(const void* A, const void* W, const float* bias, const fl
 // Workgroups per XCD of the two big-GEMM kernels (default 32 = one persistent workgroup per CU walking its share of the tiles).
 // A larger cap gives every workgroup fewer tiles (>= tiles / 8: one tile each) - the launch then frees CUs tile by tile, which
 // lets the small kernels of ANOTHER stream in between (madtp_amd/pipeline.py) at the price of the cross-tile pipelining.
-static std::atomic<int> g_wg_per_xcd{-1};
-static thread_local int t_wg_cap = 0;  // per-thread override for the launches of one library call (madtp_internal_gemm_wg_cap)
-int madtp_internal_gemm_wg_cap(int cap) { const int prev = t_wg_cap; t_wg_cap = cap > 0 ? cap : 0; return prev; }
 
 // Per-stream scheduling attributes (madtp_stream_set_sched, include/madtp_hip.h): what slice of the chip a stream owns (a CU-masked
 // stream of a caller that partitions the GPU between forwards in flight) and that caller's dispatch hints.  Readers are the launch
@@ -1046,18 +950,10 @@ extern "C" int madtp_stream_destroy(void* stream) {
     return 0;
 }
 
-// workgroups per XCD of a persistent big-GEMM launch on `stream`: the process / thread setting scaled to the CUs the stream owns
+// workgroups per XCD of a persistent big-GEMM launch on `stream`: the process setting scaled to the CUs the stream owns
 static int gemm_wg_per_xcd(const StreamSched& ss) {
-    int v = t_wg_cap;
-    if (v <= 0) {
-        v = g_wg_per_xcd.load(std::memory_order_relaxed);
-        if (v < 0) {
-            const char* e = getenv("MADTP_GEMM_WG_PER_XCD");
-            v = e ? atoi(e) : 32;
-            if (v < 1) v = 32;
-            g_wg_per_xcd.store(v, std::memory_order_relaxed);
-        }
-    }
+    static const int env = env_int("MADTP_GEMM_WG_PER_XCD", 32);
+    int v = env < 1 ? 32 : env;
     if (ss.cus_per_xcd < 32) { v = v * ss.cus_per_xcd / 32; if (v < 1) v = 1; }
     return v;
 }
@@ -1069,7 +965,7 @@ static int gemm_force_cfg() {
     if (v < 0) {
         const char* e = getenv("MADTP_GEMM_CFG");
         v = e ? atoi(e) : 0;
-        if (v < 0 || v > 10) v = 0;
+        if (v < 0 || v > 10 || v == 8) v = 0;  // (8 is retired: include/madtp_hip.h)
         g_force_cfg.store(v, std::memory_order_relaxed);
     }
     return v;
@@ -1119,7 +1015,7 @@ extern "C" float madtp_gemm_set_sq_cost(float cost) {
 }
 extern "C" int madtp_gemm_set_config(int cfg) {
     const int prev = gemm_force_cfg();
-    g_force_cfg.store((cfg < 0 || cfg > 10) ? 0 : cfg, std::memory_order_relaxed);
+    g_force_cfg.store((cfg < 0 || cfg > 10 || cfg == 8) ? 0 : cfg, std::memory_order_relaxed);
     return prev;
 }
 
@@ -1214,8 +1110,7 @@ extern "C" int madtp_splitk_sum(const float* part, int splits, size_t count, flo
 // and without it and the next GEMM loses ~3 us to the evicted lines (profiles/r02_gemm_sk_ab.txt).
 struct SkWorkspace { float* ws; int* tick; };
 static bool sk_enabled() {
-    static int sk_env = -1;
-    if (sk_env < 0) { const char* e = getenv("MADTP_GEMM_SK"); sk_env = e ? atoi(e) : 0; }
+    static const int sk_env = env_int("MADTP_GEMM_SK", 0);
     return sk_env != 0;
 }
 static bool sk_workspace(hipStream_t s, SkWorkspace& out) {
@@ -1276,8 +1171,7 @@ static int gemm_launch(const void* A, const void* W, const float* bias, const fl
     g.acc_scale = acc_scale; g.acc_scale2 = pair ? pair->acc_scale : acc_scale;
     g.ldc = (c_dtype == MADTP_BF16 || c_dtype == MADTP_F16) ? -ldc : ldc;  // negative: a 2-byte output (scalar fallback epilogue)
     g.range_flag = (c_dtype == MADTP_F16S || c_dtype == MADTP_F16) ? madtp_internal_range_flag() : nullptr;
-    static int dbg = -1;
-    if (dbg < 0) { const char* e = getenv("MADTP_GEMM_DEBUG"); dbg = e ? atoi(e) : 0; }
+    static const int dbg = env_int("MADTP_GEMM_DEBUG", 0);
     const int force_cfg = gemm_force_cfg();
     g.dbg = dbg;
     g.splitk = splitk;
@@ -1287,8 +1181,7 @@ static int gemm_launch(const void* A, const void* W, const float* bias, const fl
     g.m_dev = m_dev.p; g.m_mul = m_dev.mul;
     if (m_dev.p && (M >= 4096 || pair || splitk != 1)) return MADTP_E_SHAPE;  // device-side M: the small-tile kernels only
     {
-        static int desc_env = -1;  // MADTP_GEMM_DESC=0: gemm_kernel builds its LDS-DMA addresses per instruction (A/B runs)
-        if (desc_env < 0) { const char* e = getenv("MADTP_GEMM_DESC"); desc_env = e ? atoi(e) : 1; }
+        static const int desc_env = env_int("MADTP_GEMM_DESC", 1);  // 0: gemm_kernel builds its LDS-DMA addresses per instruction (A/B runs)
         const size_t a_bytes = ((size_t)M + 127) * (size_t)lda * esz, w_bytes = ((size_t)N + 255) * (size_t)ldw * esz;
         g.desc = desc_env && a_bytes < ((size_t)1 << 31) && w_bytes < ((size_t)1 << 31);
     }
@@ -1314,9 +1207,8 @@ static int gemm_launch(const void* A, const void* W, const float* bias, const fl
     // Thresholds of the big-tile kernels (persistent 256-row tiles): M >= 4096 and most of the chip covered - what a lone launch
     // wants (latency).  MADTP_GEMM_BIG_MIN_M / _TILES lower them (experiments with several forwards in flight, where a launch's
     // CU time counts and a 1280-row problem on 45 efficient tiles costs a third of the CU time of 720 small ones).
-    static int big_min_m = -1, big_min_t = -1;
-    if (big_min_m < 0) { const char* e = getenv("MADTP_GEMM_BIG_MIN_M"); big_min_m = e ? atoi(e) : 4096; if (big_min_m < 256) big_min_m = 256; }
-    if (big_min_t < 0) { const char* e = getenv("MADTP_GEMM_BIG_MIN_TILES"); big_min_t = e ? atoi(e) : 200; if (big_min_t < 1) big_min_t = 1; }
+    static const int big_min_m = max(env_int("MADTP_GEMM_BIG_MIN_M", 4096), 256);
+    static const int big_min_t = max(env_int("MADTP_GEMM_BIG_MIN_TILES", 200), 1);
     const int big_min_tiles = cpx == 32 ? big_min_t : (big_min_t * ncu + 255) / 256;  // "most of the chip" = most of the stream's CUs
     const bool big = !m_dev.p && M >= big_min_m && t256 >= big_min_tiles;
     const bool lp16 = ab_dtype != MADTP_F32;  // 2-byte operand planes: bf16, or f16-split (three times the slab stream)
@@ -1332,10 +1224,9 @@ static int gemm_launch(const void* A, const void* W, const float* bias, const fl
     }
     // MADTP_GEMM_CFG=5 forces the wave-specialised kernel, 1..4 force a gemm_kernel variant (A/B measurements)
     bool ws_ok = lp16 && splitk == 1 &&
-                 (force_cfg == 5 || force_cfg == 7 || force_cfg == 8 || (force_cfg == 0 && !m_dev.p && M >= big_min_m && (big || (auto_cfg == 0 && M >= 4096))));
+                 (force_cfg == 5 || force_cfg == 7 || (force_cfg == 0 && !m_dev.p && M >= big_min_m && (big || (auto_cfg == 0 && M >= 4096))));
     if (pair) {
-        static int pair_env = -1;  // MADTP_GEMM_PAIR=0: always two launches (A/B runs)
-        if (pair_env < 0) { const char* e = getenv("MADTP_GEMM_PAIR"); pair_env = e ? atoi(e) : 1; }
+        static const int pair_env = env_int("MADTP_GEMM_PAIR", 1);  // 0: always two launches (A/B runs)
         ws_ok = pair_env && lp16 && force_cfg == 0 && M >= big_min_m && 2 * t256 >= big_min_tiles && g.fast_epi &&
                 aligned16(pair->A) && aligned16(pair->W) && aligned16(pair->C) && (!pair->bias || aligned16(pair->bias));
         if (!ws_ok) return PAIR_UNSUPPORTED;
@@ -1388,15 +1279,13 @@ static int gemm_launch(const void* A, const void* W, const float* bias, const fl
                        sk_workspace(s, skw);
     if (lp16 && splitk == 1 && !pair && (K % 64) == 0 &&
         ((size_t)M + 255) * (size_t)lda * 2 < ((size_t)1 << 32) && ((size_t)N + 255) * (size_t)ldw * 2 < ((size_t)1 << 32)) {
-        static int sq_env = -1;
-        if (sq_env < 0) { const char* e = getenv("MADTP_GEMM_SQ"); sq_env = e ? atoi(e) : 1; }
+        static const int sq_env = env_int("MADTP_GEMM_SQ", 1);
         const int t_sq = ((M + 255) / 256) * ((N + 255) / 256), t_192 = ((M + 191) / 192) * ((N + 255) / 256);
         // the ping-pong main loop (gemm_pp_kernel, gemm_pp.hip) needs an even slab count; MADTP_GEMM_PP=0 keeps the lockstep kernel
         // (A/B runs), cfg 9 forces its 256-row tile, cfg 10 its 192-row tile, cfg 6 forces the lockstep kernel.  Its tile costs
         // ~1.5 tiles of 256x128 (lockstep: 1.7) - profiles/r04_gemm_pp_ab.txt; a caller's sq_cost hint (several forwards in flight)
         // applies to both.  Plain f16 and f16-split operands: the 256-column tile exists as the ping-pong kernel only.
-        static int pp_env = -1;
-        if (pp_env < 0) { const char* e = getenv("MADTP_GEMM_PP"); pp_env = e ? atoi(e) : 1; }
+        static const int pp_env = env_int("MADTP_GEMM_PP", 1);
         const bool pp_can = (K % 128) == 0;
         pp_ok = pp_can && (force_cfg == 9 || force_cfg == 10 || (force_cfg == 0 && pp_env));
         const bool sq_allowed = sq_env && ((!f16 && !x3) || pp_ok);
@@ -1406,8 +1295,7 @@ static int gemm_launch(const void* A, const void* W, const float* bias, const fl
         // Choice for an automatic launch: (1) the measured table (gemm_table.h: per (operand class, N, K, output) and 64-row bucket
         // of M the fastest of {wave-specialised 256x128, ping-pong 256x256, ping-pong 192x256} on an idle MI355X; MADTP_GEMM_TABLE=0
         // turns it off; it steps aside while a caller's in-flight hint is in force), else (2) the round-count cost model.
-        static int tab_env = -1;
-        if (tab_env < 0) { const char* e = getenv("MADTP_GEMM_TABLE"); tab_env = e ? atoi(e) : 1; }
+        static const int tab_env = env_int("MADTP_GEMM_TABLE", 1);
         int choice = -1;  // 0 wave-specialised, 1 ping-pong / lockstep 256x256, 2 ping-pong 192x256
         if (force_cfg == 6 && !f16 && !x3) choice = 1;
         else if (force_cfg == 9 && pp_can) choice = 1;
@@ -1428,6 +1316,7 @@ static int gemm_launch(const void* A, const void* W, const float* bias, const fl
         if (choice == 2) pp_rows = 192;
         if (sq_ok && !pp_ok && (f16 || x3)) sq_ok = false;  // (no lockstep instantiation for these operand formats)
     }
+    static const int grp_env = env_int("MADTP_GEMM_NGRP", -1);  // column-group width of the tile order: -1 (unset) = automatic, 0 = off, n > 0 = forced (A/B runs)
     if (sq_ok) {
         g.ntm = (M + pp_rows - 1) / pp_rows;
         g.ntn = (N + 255) / 256;
@@ -1435,8 +1324,6 @@ static int gemm_launch(const void* A, const void* W, const float* bias, const fl
             // MADTP_GEMM_NGRP: column-group width of the tile order (0 = row-panel major; unset = row-panel major up to 15 column
             // tiles - every shape of the forward - and groups of 8 beyond: with 32 column tiles (8192^3) an XCD's 32 concurrent
             // tiles then share 4 A panels and 8 W panels instead of 1 + 32: 1.32 -> 1.53-1.55 PF, profiles/r04_gemm_pp_ab.txt)
-            static int grp_env = -2;
-            if (grp_env == -2) { const char* e = getenv("MADTP_GEMM_NGRP"); grp_env = e ? atoi(e) : -1; }
             const int grp = grp_env >= 0 ? grp_env : (g.ntn >= 16 ? 8 : 0);
             g.ngrp = (grp > 0 && grp < g.ntn) ? grp : 0;
         }
@@ -1461,8 +1348,6 @@ static int gemm_launch(const void* A, const void* W, const float* bias, const fl
         g.ntn = (N + 127) / 128;
         // column groups (tile_mn): keep one group's W rows (~2.4 MB) L2-resident when W as a whole is far larger than L2
         {
-            static int grp_env = -2;  // MADTP_GEMM_NGRP: unset = automatic, 0 = off, n > 0 = forced group width (A/B runs)
-            if (grp_env == -2) { const char* e = getenv("MADTP_GEMM_NGRP"); grp_env = e ? atoi(e) : -1; }
             int G = grp_env > 0 ? grp_env : (12 * 768) / K;
             if (G < 1) G = 1;
             const bool on = grp_env > 0 || (grp_env == -1 && g.ntn >= 4 * G);
@@ -1473,25 +1358,17 @@ static int gemm_launch(const void* A, const void* W, const float* bias, const fl
         const int grid = 8 * (slots_max < cap ? slots_max : cap);
         if (sk_on && grid == 256) { g.sk = 1; g.sk_ws = skw.ws; g.sk_tick = skw.tick; }
         const size_t lds = (size_t)3 * (256 + 128) * ROWB;
-#define MADTP_LAUNCH_WS(X3_, OM_, M32_, ...)                                                                  \
+#define MADTP_LAUNCH_WS(X3_, OM_, ...)                                                                        \
     do {                                                                                                     \
-        MADTP_ENSURE_MAX_LDS((gemm_ws_kernel<X3_, OM_, M32_ __VA_OPT__(,) __VA_ARGS__>), lds);                \
-        hipLaunchKernelGGL((gemm_ws_kernel<X3_, OM_, M32_ __VA_OPT__(,) __VA_ARGS__>), dim3(grid), dim3(768), lds, s, g); \
+        MADTP_ENSURE_MAX_LDS((gemm_ws_kernel<X3_, OM_ __VA_OPT__(,) __VA_ARGS__>), lds);                      \
+        hipLaunchKernelGGL((gemm_ws_kernel<X3_, OM_ __VA_OPT__(,) __VA_ARGS__>), dim3(grid), dim3(768), lds, s, g); \
     } while (0)
-        // 32x32x16 consumer loop (bf16 operands, vector epilogue, no stream-K tail).  OFF by default - measured SLOWER than the
-        // 16x16x32 loop on every ViT shape of the forward (profiles/r03_gemm_m32_ab.txt: MFMA-only stream 1.57 vs 1.66 PF, whole
-        // kernel 623-837 vs 851-981 TF): MADTP_GEMM_M32=1 turns it on in the automatic dispatch, cfg 8 forces it (tests, A/B runs)
-        static int m32_env = -1;
-        if (m32_env < 0) { const char* e = getenv("MADTP_GEMM_M32"); m32_env = e ? atoi(e) : 0; }
-        const bool m32 = !x3 && !f16 && g.fast_epi && !g.sk && (force_cfg == 8 || (force_cfg == 0 && m32_env));
         if (f16) {
-            if (c_dtype == MADTP_F16) MADTP_LAUNCH_WS(false, OM_F16, false, true); else MADTP_LAUNCH_WS(false, OM_F32, false, true);
+            if (c_dtype == MADTP_F16) MADTP_LAUNCH_WS(false, OM_F16, true); else MADTP_LAUNCH_WS(false, OM_F32, true);
         } else if (x3) {
-            if (c_dtype == MADTP_F16S) MADTP_LAUNCH_WS(true, OM_F16S, false); else MADTP_LAUNCH_WS(true, OM_F32, false);
-        } else if (m32) {
-            if (c_dtype == MADTP_BF16) MADTP_LAUNCH_WS(false, OM_BF16, true); else MADTP_LAUNCH_WS(false, OM_F32, true);
+            if (c_dtype == MADTP_F16S) MADTP_LAUNCH_WS(true, OM_F16S); else MADTP_LAUNCH_WS(true, OM_F32);
         } else {
-            if (c_dtype == MADTP_BF16) MADTP_LAUNCH_WS(false, OM_BF16, false); else MADTP_LAUNCH_WS(false, OM_F32, false);
+            if (c_dtype == MADTP_BF16) MADTP_LAUNCH_WS(false, OM_BF16); else MADTP_LAUNCH_WS(false, OM_F32);
         }
 #undef MADTP_LAUNCH_WS
     } else if (ab_dtype == MADTP_BF16) {

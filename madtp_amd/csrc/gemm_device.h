@@ -164,99 +164,6 @@ __host__ __device__ __forceinline__ constexpr int wfrag_row(int j, int rho) {
     return LP_OUT ? 32 * (j >> 1) + 8 * (rho >> 2) + 4 * (j & 1) + (rho & 3) : 16 * j + rho;
 }
 
-// ---- 32x32x16 fragments (gemm_ws_kernel<.., M32 = true>) ---------------------------------------------------------------
-// v_mfma_f32_32x32x16_bf16 does the work of two 16x16x32 instructions in one issue slot and runs the matrix pipe at its
-// full rate (32 cycles per instruction against 2 x ~17).  Operand lane map: lane l supplies fragment row l & 31 and the 8
-// consecutive k of 16-byte chunk (l >> 5) of the 16-deep k-step; C/D: column l & 31, rows (t & 3) + 8 (t >> 2) + 4 (l >> 5)
-// for register t.  With the operands swapped (D = Wfrag . Afrag^T) lane (l32 = l & 31, h = l >> 5) holds output row
-// 32 i + l32 and, per fragment (i, j), sixteen columns in four runs of four consecutive W-fragment rows 8 q + 4 h + e.
-//   f32 out : W-fragment row rho of fragment j is tile column 32 j + rho                 -> float4 per (i, j, q)
-//   bf16 out: W-fragment row rho is tile column 32 j + swap(bit 2, bit 3)(rho)           -> registers 8p..8p+7 are the 8
-//             consecutive columns 32 j + 16 p + 8 h .. +7 = one 16-byte store per (i, j, p)
-// LDS swizzle of the M32 stage image: a ds_read_b128 is serviced in 16-lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}
-// (+32): the 16 rows of a group (same chunk) must fall on 16 different 16-byte slots of the 256-byte bank row, i.e. the
-// key must take all 8 values over the 8 even and over the 8 odd rows of a group - (r >> 1) & 7 does (the bf16-output row
-// permutation maps each group onto itself).  One key function for both operands.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-__host__ __device__ __forceinline__ constexpr int swz_key32(int r) { return (r >> 1) & 7; }
-template <bool LP_OUT>
-__host__ __device__ __forceinline__ constexpr int wfrag_row32(int j, int rho) {
-    return 32 * j + (LP_OUT ? ((rho & ~12) | ((rho & 4) << 1) | ((rho & 8) >> 1)) : rho);
-}
-
-// epilogue of one consumer wave's 64x64 block held as 2x2 fragments of 32x32 (fast path only: the launcher keeps shapes
-// that need the scalar fallback on the 16x16 kernel).  Same structure as epilogue(): every load first, one wait, then
-// descriptor-bounded 16-byte stores; the f32 residual is fetched per 32-row fragment row.
-template <int OM, int ACT, bool HAS_RES>
-__device__ __forceinline__ void epilogue32(const GemmArgs& g, const f32x16 (&acc)[2][2], int row_t, int col_w, int l32, int h) {
-    constexpr bool LP_OUT = OM != OM_F32;
-    constexpr bool FAST_ACT = OM == OM_BF16 || OM == OM_F16;
-    constexpr int CSZ = LP_OUT ? 2 : 4;
-    constexpr int NJ = LP_OUT ? 2 : 4;   // column vectors per lane, fragment row and fragment column: p (8 columns) or q (4)
-    constexpr int NV = LP_OUT ? 2 : 1;   // float4s per column vector
-    const int ldc = g.ldc < 0 ? -g.ldc : g.ldc;
-    const int rows_valid = max(min(g.M - row_t, 64), 0);
-    const unsigned long long cb = (unsigned long long)((char*)g.C + (size_t)row_t * ldc * CSZ);
-    const unsigned cb_lo = __builtin_amdgcn_readfirstlane((unsigned)cb);
-    const unsigned cb_hi = __builtin_amdgcn_readfirstlane((unsigned)(cb >> 32));
-    const __amdgpu_buffer_rsrc_t crsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(((unsigned long long)cb_hi << 32) | cb_lo), 0, __builtin_amdgcn_readfirstlane(rows_valid * ldc * CSZ), 0x00020000);
-    // one pass per fragment column j (32 output columns): its bias and - f32 residual stream - the residual of both fragment
-    // rows are fetched first, ONE wait, then the 2 x NJ stores: two exposed round trips per 64x64 block, 48 live load registers
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        int colv[NJ];
-        bool cok[NJ];
-        f32x4 bv[NJ][NV];
-#pragma unroll
-        for (int jv = 0; jv < NJ; ++jv) {
-            colv[jv] = col_w + 32 * j + (LP_OUT ? 16 * jv + 8 * h : 8 * jv + 4 * h);
-            cok[jv] = colv[jv] < g.N;
-#pragma unroll
-            for (int u = 0; u < NV; ++u) bv[jv][u] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-        if (g.bias) {  // uniform; the unconditional wait below closes this diamond
-#pragma unroll
-            for (int jv = 0; jv < NJ; ++jv)
-#pragma unroll
-                for (int u = 0; u < NV; ++u) bv[jv][u] = *(const f32x4*)(g.bias + (cok[jv] ? colv[jv] : 0) + 4 * u);
-        }
-        f32x4 rv[HAS_RES ? 2 : 1][HAS_RES ? NJ : 1];
-        if constexpr (HAS_RES) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int row = min(row_t + 32 * i + l32, g.M - 1);
-#pragma unroll
-                for (int jv = 0; jv < NJ; ++jv)
-                    rv[i][jv] = *(const f32x4*)(g.residual + (size_t)row * g.ldr + (cok[jv] ? colv[jv] : 0));
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) (the first one also covers the previous tile's stores, a main loop old)
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int jv = 0; jv < NJ; ++jv) {
-                const int t0 = LP_OUT ? 8 * jv : 4 * jv;  // first accumulator register of this column vector
-                f32x4 v[NV];
-#pragma unroll
-                for (int u = 0; u < NV; ++u) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        v[u][e] = epi_act<FAST_ACT, ACT>(fmaf(acc[i][j][t0 + 4 * u + e], g.acc_scale, bv[jv][u][e])) * g.out_scale;
-                    if constexpr (HAS_RES) v[u] += rv[i][jv];
-                }
-                const unsigned off = cok[jv] ? (unsigned)((32 * i + l32) * ldc + colv[jv]) * CSZ : 0x80000000u;
-                u32x4 bits;
-                if constexpr (OM == OM_BF16) bits = __builtin_bit_cast(u32x4, pack_bf16x8(v[0], v[1]));
-                else if constexpr (OM == OM_F16) bits = __builtin_bit_cast(u32x4, pack_f16x8(v[0], v[1]));
-                else bits = __builtin_bit_cast(u32x4, v[0]);
-                __builtin_amdgcn_raw_buffer_store_b128(bits, crsrc, off, 0, 0);
-            }
-    }
-}
-
 // HAS_RES: the residual is read by the epilogue itself (kernels that do not prefetch it into `res`); compile-time so
 // that the fast path below is straight-line code.
 template <int OM, int ACT, bool HAS_RES, int FM, int FN, int BM, int BN, bool FAST_ONLY = false, int RM = 1, int RN = 1>

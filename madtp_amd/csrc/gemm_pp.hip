@@ -290,8 +290,7 @@ __attribute__((visibility("hidden"))) int madtp_gemm_pp_launch(const void* args,
     const GemmArgs& g = *(const GemmArgs*)args;
     hipStream_t s = (hipStream_t)stream;
     const size_t lds = (size_t)8 * 128 * ROWB;
-    static int abl = -1;  // MADTP_PP_ABLATE: timing experiments (bf16 operands and output, 256-row tile only; see ABL above)
-    if (abl < 0) { const char* e = getenv("MADTP_PP_ABLATE"); abl = e ? atoi(e) : 0; }
+    static const int abl = env_int("MADTP_PP_ABLATE", 0);  // timing experiments (bf16 operands and output, 256-row tile only; see ABL above)
 #define PP_LAUNCH(OM_, MODE_, FA_, ABL_)                                                                        \
     do {                                                                                                        \
         MADTP_ENSURE_MAX_LDS((gemm_pp_kernel<OM_, MODE_, FA_, ABL_>), lds);                                      \

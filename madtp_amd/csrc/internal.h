@@ -29,10 +29,6 @@ MADTP_INTERNAL int madtp_i_token_gather_ln_dev(const float* x, const int32_t* ds
                                                int lp_dtype, const int32_t* dims_l, void* stream);
 MADTP_INTERNAL int madtp_i_align_logits(const float* x, const void* sd_hi, const void* sd_lo, float* out, int M, int dim, int split_dtype,
                                         float out_scale, DevN m_dev, void* stream);
-// Workgroups per XCD of the big-GEMM kernels for the following launches of THIS thread (0 = the process-wide setting); returns the
-// previous value.  The encoder call's side-stream K/V projections run on part of the chip so that the latency-bound text kernels
-// of the main stream keep finding free CUs.
-MADTP_INTERNAL int madtp_internal_gemm_wg_cap(int cap);
 // ---- device-side lengths for the text encoders (madtp_bert_encoder_async) ----
 MADTP_INTERNAL int madtp_i_cast_lp(const float* src, void* dst, size_t n, int lp_dtype, float scale, DevN n_dev, void* stream);
 MADTP_INTERNAL int madtp_i_attention_mask(const void* q, const void* k, const void* v, void* out, const float* add_mask, float* colsum_part,
@@ -44,16 +40,20 @@ MADTP_INTERNAL int madtp_i_attention_cross(const void* q, const void* k, const v
 MADTP_INTERNAL int madtp_i_attention_pair(const void* q0, const void* q1, const void* k0, const void* k1, const void* v0, const void* v1,
                                           const int32_t* kv_batch_index, void* out0, void* out1, const float* add_mask0,
                                           const float* add_mask1, int B, int H, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo,
-                                          float scale, int io_dtype, const int32_t* nq_dev, void* stream);
+                                          float scale, int io_dtype, int split_dim, const int32_t* nq_dev, void* stream);
 // additive-mask compaction with N, k from dims_l (k == 0: copy); MED: indices then the (k+1)-th of indices_sort, NLVR: indices_sort
 MADTP_INTERNAL int madtp_i_mask_gather_dev(const float* mask, const int64_t* indices, const int64_t* indices_sort, int variant_nlvr,
                                            float* out, int B, const int32_t* dims_l, void* stream);
 // incremental decoding: Nq queries per sample against the first Nk rows of the sample's K/V block of kv_block_rows rows
 MADTP_INTERNAL int madtp_i_attention_cached(const void* q, const void* k, const void* v, int kv_block_rows, void* out, int B, int H, int Nq,
                                             int Nk, int ldq, int ldk, int ldv, int ldo, float scale, int io_dtype, void* stream);
-// f16x3 layer calls: ask the next attention launches of this thread (io_dtype MADTP_F16S) to write their context as the f16-split
-// operand planes of the consuming GEMM (out = _Float16 planes, ldo in f16 elements, P1 at column offset split_dim); 0 = off.
-// _done(): 1 once a launch honoured the request.  _f16s_enabled(): the f16s attention kernels are on (MADTP_ATTN_F16S != 0).
-MADTP_INTERNAL int madtp_internal_attn_split_out(int split_dim);
-MADTP_INTERNAL int madtp_internal_attn_split_done();
-MADTP_INTERNAL bool madtp_internal_attn_f16s_enabled();
+// The launcher behind every madtp_attention* entry point (those pass split_dim = 0).  split_dim > 0, f16x3 layer calls only
+// (io_dtype MADTP_F16S): the context is written as the f16-split operand planes of the consuming GEMM (out = _Float16 planes, ldo
+// in f16 elements, P1 at column offset split_dim); MADTP_E_BADARG unless madtp_internal_attn_f16s_enabled().
+// madtp_i_attention_pair takes the same argument for its two-launch form (its one-launch form writes no planes: MADTP_E_BADARG).
+MADTP_INTERNAL int madtp_i_attention_launch(const void* q, const void* k, const void* v, const int32_t* kv_batch_index, void* out,
+                                            const float* add_mask, const float* mask_qk, int ld_mask_qk, float* colsum_part, float* p0,
+                                            float* onorm, int B, int H, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, float scale,
+                                            int io_dtype, int split_dim, void* stream, const int32_t* n_dev = nullptr,
+                                            int dev_q_only = 0, int kv_block_rows = 0);
+MADTP_INTERNAL bool madtp_internal_attn_f16s_enabled();  // the f16s attention kernels are on (MADTP_ATTN_F16S != 0)

@@ -1321,154 +1321,17 @@ constexpr size_t att_ft_mma_lds(bool split) {
 // ------------------------------------------------------------------------------------- alignment logits (bf16 x 3)
 // token_attn = x @ sd^T for the fast mode: f32 accuracy class on the bf16 matrix cores via a two-term split
 // x = xh + xl, sd = sh + sl (bf16 each):  x.sd ~= xh.sh + xl.sh + xh.sl  (the dropped xl.sl term is 2^-16 relative).
-// x rows are read as f32 straight into registers and split there; the 128 dictionary rows (hi and lo slabs) are
-// LDS-DMA'd in 128-byte K slabs with the GEMM kernel's swizzle; workgroup = 64 token rows x 128 columns, one 16-row
-// MFMA fragment per wave, operand-swapped MFMA so each lane stores float4s.
-constexpr int AL_ROWB = 128, AL_TILE = 128 * AL_ROWB, AL_STAGES = 3;
-// MADTP_AL_ABLATE (tools/build_ablate.py, timing experiments only): bit 0 drops the MFMAs, bit 1 the x loads, bit 2 the
-// LDS-DMAs, bit 3 the fragment reads.
-#ifndef MADTP_AL_ABLATE
-#define MADTP_AL_ABLATE 0
-#endif
-// NK = dim/64 as a compile-time constant fully unrolls the slab loop: in a rolled loop the compiler carries the in-flight
-// x registers through copies at the back edge, and a copy of a pending load is a wait for it (NK = 0: runtime loop).
-template <int NK>
-__global__ __launch_bounds__(256, 1) void align_logits_kernel(const float* __restrict__ x, const char* __restrict__ sd_hi,
-                                                              const char* __restrict__ sd_lo, float* __restrict__ out, int M,
-                                                              int dim, DevN m_dev) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];  // AL_STAGES x (hi tile, lo tile) = 96 KiB
-    M = devn(m_dev, M);
-    if ((int)blockIdx.x * 64 >= M) return;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l16 = lane & 15, g = lane >> 4;
-    const int m0 = blockIdx.x * 64 + wave * 16;
-    const int row = min(m0 + l16, M - 1);
-    const float* xr = x + (size_t)row * dim;
-    const int nk = NK ? NK : dim * 2 / AL_ROWB;
-    const int sub = lane >> 3, chunk_src = (lane & 7) ^ sub;
-    auto stage = [&](int kt) {  // 8 LDS-DMA instructions per wave
-        char* base = smem + (kt % AL_STAGES) * 2 * AL_TILE;
-        if (MADTP_AL_ABLATE & 4) return;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int grp = wave * 4 + q;
-            const size_t src = ((size_t)(grp * 8 + sub) * dim) * 2 + (size_t)kt * AL_ROWB + chunk_src * 16;
-            __builtin_amdgcn_global_load_lds(GLOBAL_PTR(sd_hi + src), LDS_PTR(base + grp * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds(GLOBAL_PTR(sd_lo + src), LDS_PTR(base + AL_TILE + grp * 1024), 16, 0, 0);
-        }
-    };
-    f32x4 acc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    // this lane's x slice of a slab: k = 64kt + 32kk + 8g .. +7, read as f32 straight into registers TWO slabs ahead
-    // (the HBM latency of the token rows hides under two slabs of MFMAs); the dictionary slabs run two ahead as well,
-    // through a 3-stage LDS ring synchronised with a counted s_waitcnt.
-    f32x4 xq[2][2][2];  // register set kt&1 holds x(kt); it is refilled with x(kt+2) as soon as it has been split
-    auto load_x = [&](int kt, f32x4 (&d)[2][2]) {
-        if ((MADTP_AL_ABLATE & 2) && kt > 1) return;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const float* p = xr + kt * 64 + kk * 32 + g * 8;
-            d[kk][0] = *(const f32x4*)p;
-            d[kk][1] = *(const f32x4*)(p + 4);
-        }
-    };
-    load_x(0, xq[0]);
-    stage(0);
-    load_x(1, xq[1]);  // nk is even (dim % 128 == 0, checked by the launcher)
-    stage(1);
-    auto slab = [&](int kt, f32x4 (&xs)[2][2]) {
-        // vmcnt is one in-order counter: slab kt (and x(kt)) were issued two iterations ago, so everything issued in
-        // the previous iteration - 4 x loads + 8 DMAs - may still be in flight
-        if (MADTP_AL_ABLATE & 6) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        // raw barrier, no fence: a fence would drain the LDS-DMAs in flight (the compiler tracks them as pending LDS
-        // writes); the counted wait above is what makes slab kt visible, and every ds_read of slab kt-1 has been
-        // consumed by an MFMA before its wave gets here
-        __builtin_amdgcn_s_barrier();
-        bf16x8 ah[2], al[2];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            ah[kk] = pack_bf16x8(xs[kk][0], xs[kk][1]);
-            f32x4 r0, r1;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                r0[e] = xs[kk][0][e] - bf16_to_f32((bf16_t)ah[kk][e]);
-                r1[e] = xs[kk][1][e] - bf16_to_f32((bf16_t)ah[kk][4 + e]);
-            }
-            al[kk] = pack_bf16x8(r0, r1);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (kt + 2 < nk) { load_x(kt + 2, xs); stage(kt + 2); }
-        const char* sh = smem + (kt % AL_STAGES) * 2 * AL_TILE;
-        const char* sl = sh + AL_TILE;
-        // Each accumulator's three products are issued in three passes over the 8 column tiles, so consecutive MFMAs
-        // never depend on each other (the order per accumulator - hi.hi, hi.lo, lo.hi - and therefore the result is
-        // unchanged); the kk=1 fragments are read under the first kk=0 pass (lgkmcnt is a 4-bit counter: at most 16
-        // reads are kept in flight).
-        bf16x8 bh[2][8], bl[2][8];
-        auto read_frags = [&](int kk) {
-            if ((MADTP_AL_ABLATE & 8) && kt > 0) return;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int rb = j * 16 + l16;
-                const int off = rb * AL_ROWB + (((kk * 4 + g) ^ (rb & 7)) << 4);
-                bh[kk][j] = *(const bf16x8*)(sh + off);
-                bl[kk][j] = *(const bf16x8*)(sl + off);
-            }
-        };
-        read_frags(0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(MADTP_AL_ABLATE & 1))
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[0][j], ah[0], acc[j], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        read_frags(1);
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(MADTP_AL_ABLATE & 1)) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[0][j], al[0], acc[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[0][j], ah[0], acc[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[1][j], ah[1], acc[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[1][j], al[1], acc[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[1][j], ah[1], acc[j], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    if constexpr (NK > 0) {
-#pragma unroll
-        for (int kt = 0; kt < NK; kt += 2) {
-            slab(kt, xq[0]);
-            slab(kt + 1, xq[1]);
-        }
-    } else {
-        for (int kt = 0; kt < nk; kt += 2) {
-            slab(kt, xq[0]);
-            slab(kt + 1, xq[1]);
-        }
-    }
-    if (m0 + l16 < M) {
-        float* o = out + (size_t)(m0 + l16) * 128 + 4 * g;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) *(f32x4*)(o + 16 * j) = acc[j];
-    }
-}
-
-// Wave-specialised variant (the one the fast mode runs): workgroup = 64 token rows x 128 columns as 8 CONSUMER waves (4 row
+// The 128 dictionary rows (hi and lo slabs) travel in 128-byte K slabs with the GEMM kernel's swizzle; operand-swapped MFMA so
+// each lane stores float4s.
+// Wave-specialised: workgroup = 64 token rows x 128 columns as 8 CONSUMER waves (4 row
 // tiles x 2 column halves: two MFMA instruction streams per SIMD) + 4 LOADER waves that LDS-DMA the f32 token rows (64 x
 // 256 B per K slab) and the dictionary hi/lo slabs into a 3-stage 144 KiB ring with counted vmcnt waits, one raw barrier per
-// slab.  The consumers never touch vector memory until their epilogue, so no HBM latency sits in the MFMA stream (the
-// register-prefetching kernel above loses ~7 us per launch to it).  x rows are swizzled with chunk ^= row&15 (256-byte rows
-// span all 64 banks), the dictionary with the GEMM swizzle.
+// slab.  The consumers never touch vector memory until their epilogue, so no HBM latency sits in the MFMA stream.
+// x rows are swizzled with chunk ^= row&15 (256-byte rows span all 64 banks), the dictionary with the GEMM swizzle.
 // F16 = true is the fp32-ACCURATE flavour (precision mode "f16x3"): the dictionary arrives as the f16 planes Q0 / Q1 of
 // sd * 2^s (common.h), x is split in registers into P0 = f16(x), P1 = f16((x - P0) 2^11), the three products
 // P0 Q0 + P0 Q1 + P1 (Q0 2^-11) run on the f16 MFMA and the accumulators are scaled by out_scale = 2^-s.
+constexpr int AL_ROWB = 128, AL_TILE = 128 * AL_ROWB;  // one dictionary slab: 128 rows x 128 B
 constexpr int AW_XT = 64 * 256, AW_STAGE = AW_XT + 2 * AL_TILE;  // 16 KiB + 2 x 16 KiB
 template <bool F16>
 __global__ __launch_bounds__(768, 1) void align_ws_kernel(const float* __restrict__ x, const char* __restrict__ sd_hi,
@@ -1584,7 +1447,7 @@ __global__ __launch_bounds__(768, 1) void align_ws_kernel(const float* __restric
             }
             al[kk] = pack_bf16x8(r0, r1);
         }
-        // per accumulator: hi.hi, hi.lo, lo.hi (kk = 0), then the same for kk = 1 - the order of the kernel above
+        // per accumulator: hi.hi, hi.lo, lo.hi (kk = 0), then the same for kk = 1
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
@@ -1604,159 +1467,6 @@ __global__ __launch_bounds__(768, 1) void align_ws_kernel(const float* __restric
     }
 }
 
-// 128-row variant of align_ws_kernel (round 6; the "taller row tile" of DESIGN section 9): one workgroup streams the split dictionary
-// for 128 token rows instead of 64 - half the workgroups and half the dictionary bytes per launch.  Per K slab: 32 KiB of x rows +
-// 2 x 16 KiB of dictionary = 64 KiB, TWO stages (three would not fit 160 KiB): consumers signal "fragments of slab kt are in
-// registers" with a second barrier, after which the loaders refill that stage under the slab's MFMAs.  8 consumer waves = 4 row
-// groups of 32 rows x 2 column halves: a wave's dictionary fragments serve two row tiles (half the LDS fragment reads per MFMA).
-// Per accumulator the product order over (slab, kk, term) is align_ws_kernel's: the same bits.
-constexpr int AW2_XT = 128 * 256, AW2_STAGE = AW2_XT + 2 * AL_TILE;  // 32 KiB + 2 x 16 KiB
-template <bool F16>
-__global__ __launch_bounds__(768, 1) void align_ws2_kernel(const float* __restrict__ x, const char* __restrict__ sd_hi,
-                                                           const char* __restrict__ sd_lo, float* __restrict__ out, int M, int dim,
-                                                           float out_scale, DevN m_dev) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    M = devn(m_dev, M);
-    if ((int)blockIdx.x * 128 >= M) return;
-    constexpr int STAGES = 2, PER = 16;  // 64 one-KiB DMA instructions per slab, 16 per loader wave
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nk = dim / 64;
-    const int row0 = blockIdx.x * 128;
-    if (wave >= 8) {
-        // ------------------------------------------ loader ------------------------------------------
-        const int lw = wave - 8;
-        const char* srcp[PER];
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            const int idx = lw * PER + q;  // 0..31: x groups of 4 rows; 32..47: hi groups of 8 rows; 48..63: lo groups
-            if (idx < 32) {
-                const int r = idx * 4 + (lane >> 4);
-                int row = row0 + r;
-                row = row < M ? row : M - 1;
-                srcp[q] = (const char*)(x + (size_t)row * dim) + (((lane & 15) ^ (r & 15)) << 4);
-            } else {
-                const int grp = (idx - 32) & 15, r = grp * 8 + (lane >> 3);
-                const char* base = idx < 48 ? sd_hi : sd_lo;
-                srcp[q] = base + (size_t)r * dim * 2 + (((lane & 7) ^ (r & 7)) << 4);
-            }
-        }
-        auto issue = [&](int kt) {
-            char* st = smem + (kt % STAGES) * AW2_STAGE + lw * PER * 1024;
-#pragma unroll
-            for (int q = 0; q < PER; ++q) {
-                const int idx = lw * PER + q;
-                const int koff = idx < 32 ? kt * 256 : kt * 128;
-                __builtin_amdgcn_global_load_lds(GLOBAL_PTR(srcp[q] + koff), LDS_PTR(st + q * 1024), 16, 0, 0);
-            }
-        };
-        issue(0);
-        if (nk > 1) issue(1);
-        for (int kt = 0; kt < nk; ++kt) {
-            if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");  // only slab kt+1 may still fly
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();  // A: slab kt landed
-            __builtin_amdgcn_s_barrier();  // B: every consumer holds slab kt's fragments in registers
-            if (kt + 2 < nk) issue(kt + 2);  // into the stage slab kt used
-        }
-        return;
-    }
-    // ------------------------------------------ consumer ------------------------------------------
-    const int l16 = lane & 15, g = lane >> 4;
-    const int rg = wave & 3, cw = wave >> 2;
-    f32x4 acc[2][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[t][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    for (int kt = 0; kt < nk; ++kt) {
-        const char* st = smem + (kt % STAGES) * AW2_STAGE;
-        const char* sh = st + AW2_XT;
-        const char* sl = sh + AL_TILE;
-        __builtin_amdgcn_s_barrier();  // A
-        f32x4 xa[2][2][2];
-        bf16x8 bh[2][4], bl[2][4];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const int xr = rg * 32 + t * 16 + l16;
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const int c = kk * 8 + g * 2;
-                xa[t][kk][0] = *(const f32x4*)(st + xr * 256 + (((c + 0) ^ (xr & 15)) << 4));
-                xa[t][kk][1] = *(const f32x4*)(st + xr * 256 + (((c + 1) ^ (xr & 15)) << 4));
-            }
-        }
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int rb = (cw * 4 + j) * 16 + l16;
-                const int off = rb * AL_ROWB + (((kk * 4 + g) ^ (rb & 7)) << 4);
-                bh[kk][j] = *(const bf16x8*)(sh + off);
-                bl[kk][j] = *(const bf16x8*)(sl + off);
-            }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();  // B: the stage may be refilled
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            bf16x8 ah[2], al[2];
-            if constexpr (F16) {
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    u32x4 p0, p1;
-                    split_f16x8(xa[t][kk][0], xa[t][kk][1], p0, p1);
-                    ah[kk] = __builtin_bit_cast(bf16x8, p0);
-                    al[kk] = __builtin_bit_cast(bf16x8, p1);
-                }
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, bl[kk][j]), __builtin_bit_cast(f16x8, ah[kk]), acc[t][j], 0, 0, 0);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, bh[kk][j]), __builtin_bit_cast(f16x8, ah[kk]), acc[t][j], 0, 0, 0);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const f16x8 q2 = __builtin_bit_cast(f16x8, bh[kk][j]) * (_Float16)(1.0f / F16S_LO_SCALE);
-                        acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(q2, __builtin_bit_cast(f16x8, al[kk]), acc[t][j], 0, 0, 0);
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    ah[kk] = pack_bf16x8(xa[t][kk][0], xa[t][kk][1]);
-                    f32x4 r0, r1;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        r0[e] = xa[t][kk][0][e] - bf16_to_f32((bf16_t)ah[kk][e]);
-                        r1[e] = xa[t][kk][1][e] - bf16_to_f32((bf16_t)ah[kk][4 + e]);
-                    }
-                    al[kk] = pack_bf16x8(r0, r1);
-                }
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[kk][j], ah[kk], acc[t][j], 0, 0, 0);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bh[kk][j], al[kk], acc[t][j], 0, 0, 0);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bl[kk][j], ah[kk], acc[t][j], 0, 0, 0);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int m = row0 + rg * 32 + t * 16 + l16;
-        if (m < M) {
-            float* o = out + (size_t)m * 128 + cw * 64 + 4 * g;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) *(f32x4*)(o + 16 * j) = F16 ? acc[t][j] * out_scale : acc[t][j];
-        }
-    }
-}
-
 }  // namespace
 
 constexpr int SPLIT_MAX_B = 1024, SPLIT_MAX_G = 8;  // per-slot scratch of token_score_split_kernel
@@ -1767,8 +1477,7 @@ static bool score_fast() { return g_score_fast.load(std::memory_order_relaxed) !
 extern "C" int madtp_set_score_fast(int on) { return g_score_fast.exchange(on ? 1 : 0, std::memory_order_relaxed); }
 
 static bool split_enabled() {  // MADTP_TS_SPLIT=0: always one workgroup per sample (A/B runs)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MADTP_TS_SPLIT"); v = e ? atoi(e) : 1; }
+    static const int v = env_int("MADTP_TS_SPLIT", 1);
     return v != 0;
 }
 
@@ -2038,8 +1747,7 @@ int madtp_i_token_gather_ln_dev(const float* x, const int32_t* dst_pos, const fl
 }
 
 static bool rank_split_enabled() {  // MADTP_RANK_SPLIT=0: the one-workgroup ranking at every length (A/B runs)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("MADTP_RANK_SPLIT"); v = e ? atoi(e) : 1; }
+    static const int v = env_int("MADTP_RANK_SPLIT", 1);
     return v != 0;
 }
 
@@ -2200,53 +1908,20 @@ extern "C" int madtp_align_logits(const float* x, const void* sd_hi, const void*
                                   int split_dtype, float out_scale, void* stream) {
     return madtp_i_align_logits(x, sd_hi, sd_lo, out, M, dim, split_dtype, out_scale, DevN{nullptr, 0, 0}, stream);
 }
-// tile height of the wave-specialised alignment kernel when MADTP_ALIGN_ROWS does not force one (set from the measurement,
-// profiles/r06_align_rows_ab.txt)
-static int align_rows_auto(int M) { (void)M; return 64; }
-
 int madtp_i_align_logits(const float* x, const void* sd_hi, const void* sd_lo, float* out, int M, int dim, int split_dtype,
                          float out_scale, DevN m_dev, void* stream) {
     if (!x || !sd_hi || !sd_lo || !out || M <= 0) return MADTP_E_BADARG;
     if (split_dtype != MADTP_BF16 && split_dtype != MADTP_F16S) return MADTP_E_DTYPE;
     if (dim % 128) return MADTP_E_SHAPE;
     if (!aligned16(x) || !aligned16(sd_hi) || !aligned16(sd_lo) || !aligned16(out)) return MADTP_E_ALIGN;
-    constexpr int lds = AL_STAGES * 2 * AL_TILE;
-    MADTP_ENSURE_MAX_LDS(align_logits_kernel<12>, lds);
-    MADTP_ENSURE_MAX_LDS(align_logits_kernel<8>, lds);
-    MADTP_ENSURE_MAX_LDS(align_logits_kernel<0>, lds);
-    static int variant = -1;  // MADTP_ALIGN_KERNEL=1 selects the register-prefetching kernel (A/B measurements)
-    if (variant < 0) { const char* e = getenv("MADTP_ALIGN_KERNEL"); variant = e ? atoi(e) : 0; }
-    // MADTP_ALIGN_ROWS: 64 (align_ws_kernel), 128 (align_ws2_kernel), 0 = automatic (see align_rows_auto)
-    static int rows_env = -1;
-    if (rows_env < 0) { const char* e = getenv("MADTP_ALIGN_ROWS"); rows_env = e ? atoi(e) : 0; }
-    const int rows_sel = rows_env == 64 || rows_env == 128 ? rows_env : align_rows_auto(M);
-    if ((variant == 0 || split_dtype == MADTP_F16S) && rows_sel == 128 && !m_dev.p) {
-        MADTP_ENSURE_MAX_LDS(align_ws2_kernel<false>, 2 * AW2_STAGE);
-        MADTP_ENSURE_MAX_LDS(align_ws2_kernel<true>, 2 * AW2_STAGE);
-        if (split_dtype == MADTP_F16S)
-            hipLaunchKernelGGL(align_ws2_kernel<true>, dim3((M + 127) / 128), dim3(768), 2 * AW2_STAGE, (hipStream_t)stream, x,
-                               (const char*)sd_hi, (const char*)sd_lo, out, M, dim, out_scale, m_dev);
-        else
-            hipLaunchKernelGGL(align_ws2_kernel<false>, dim3((M + 127) / 128), dim3(768), 2 * AW2_STAGE, (hipStream_t)stream, x,
-                               (const char*)sd_hi, (const char*)sd_lo, out, M, dim, 1.f, m_dev);
-        MADTP_LAUNCH_CHECK();
-        return 0;
-    }
-    if (variant == 0 || split_dtype == MADTP_F16S) {
-        MADTP_ENSURE_MAX_LDS(align_ws_kernel<false>, 3 * AW_STAGE);
-        MADTP_ENSURE_MAX_LDS(align_ws_kernel<true>, 3 * AW_STAGE);
-        if (split_dtype == MADTP_F16S)
-            hipLaunchKernelGGL(align_ws_kernel<true>, dim3((M + 63) / 64), dim3(768), 3 * AW_STAGE, (hipStream_t)stream, x,
-                               (const char*)sd_hi, (const char*)sd_lo, out, M, dim, out_scale, m_dev);
-        else
-            hipLaunchKernelGGL(align_ws_kernel<false>, dim3((M + 63) / 64), dim3(768), 3 * AW_STAGE, (hipStream_t)stream, x,
-                               (const char*)sd_hi, (const char*)sd_lo, out, M, dim, 1.f, m_dev);
-        MADTP_LAUNCH_CHECK();
-        return 0;
-    }
-    auto kern = dim == 768 ? align_logits_kernel<12> : dim == 512 ? align_logits_kernel<8> : align_logits_kernel<0>;
-    hipLaunchKernelGGL(kern, dim3((M + 63) / 64), dim3(256), lds, (hipStream_t)stream, x, (const char*)sd_hi,
-                       (const char*)sd_lo, out, M, dim, m_dev);
+    MADTP_ENSURE_MAX_LDS(align_ws_kernel<false>, 3 * AW_STAGE);
+    MADTP_ENSURE_MAX_LDS(align_ws_kernel<true>, 3 * AW_STAGE);
+    if (split_dtype == MADTP_F16S)
+        hipLaunchKernelGGL(align_ws_kernel<true>, dim3((M + 63) / 64), dim3(768), 3 * AW_STAGE, (hipStream_t)stream, x,
+                           (const char*)sd_hi, (const char*)sd_lo, out, M, dim, out_scale, m_dev);
+    else
+        hipLaunchKernelGGL(align_ws_kernel<false>, dim3((M + 63) / 64), dim3(768), 3 * AW_STAGE, (hipStream_t)stream, x,
+                           (const char*)sd_hi, (const char*)sd_lo, out, M, dim, 1.f, m_dev);
     MADTP_LAUNCH_CHECK();
     return 0;
 }

@@ -124,7 +124,7 @@ def test_headline_batch_index_match(env):
     (b) bf16: per-layer decisions sound (teacher-forced), free-running sets / logits within about half the measured slack
         (MI355X, round 2: exact 0.17, Jaccard 0.68, teacher-forced exact 0.868 / Jaccard 0.998, |dlogit| 0.02), and the
         count-flip report names the layer where k = max_b count first leaves the oracle's (the cascade's start);
-    (c) the batch-dependent GEMM dispatch (256x256 / 32x32x16 kernels vs the 16x16x32 wave-specialised one) adds no error:
+    (c) the batch-dependent GEMM dispatch (256x256 kernels vs the 256x128 wave-specialised one) adds no error:
         the teacher-forced figures under madtp_gemm_set_config(7) are the same within noise."""
     from madtp_amd import configs, hip
     from oracle.index_match import nlvr_index_match

@@ -5,7 +5,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 from madtp_amd import build as b
 
 b.build()
-src, macro = {"align": ("prune.hip", "MADTP_AL_ABLATE"), "tstime": ("prune.hip", "MADTP_TS_TIMING"), "attime": ("attention.hip", "MADTP_TS_TIMING"),
+src, macro = {"tstime": ("prune.hip", "MADTP_TS_TIMING"), "attime": ("attention.hip", "MADTP_TS_TIMING"),
              "wstime": ("gemm.hip", "MADTP_WS_TIMING"), "sq": ("gemm.hip", "MADTP_SQ_ABLATE")}.get(
     os.environ.get("ABLATE"), ("gemm.hip", "MADTP_WS_ABLATE"))
 for n in [int(a) for a in sys.argv[1:]] or [1, 2, 3, 4]:
