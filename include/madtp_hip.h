@@ -71,17 +71,22 @@ int madtp_gemm(const void* A, const void* W, const float* bias, const float* res
  * variable MADTP_GEMM_CFG sets the initial value.  No reference counterpart (the reference has one GEMM: aten::addmm).
  * Returns the previous value. */
 int madtp_gemm_set_config(int cfg);
-/* Scheduling hint for the automatic dispatch: the relative per-round cost of a 256x256 tile against a 256x128 tile (default
- * 1.7 = an isolated launch; a caller that keeps several forwards in flight on the GPU lowers it - the other streams fill
- * sparse last rounds, so the more efficient tile wins more often).  cost <= 0 restores the default (MADTP_GEMM_SQ_COST or
- * 1.7).  Process-wide; results do not depend on it (same arithmetic per output element in both kernels).  Returns the previous
- * value.  No reference counterpart. */
-float madtp_gemm_set_sq_cost(float cost);
-/* Second scheduling hint of the same kind: the tile configuration of the SMALL problems (fewer than 200 tiles of 256x128, e.g.
- * the 1280-row GEMMs of the text encoders): -1 = automatic (the smallest tile that fits one round: lowest latency of a lone
- * launch), 0 = 128x128, 1 = 64x128, 2 = 64x128 with three stages, 3 = 64x64.  A caller with several forwards in flight sets 0
- * (fewer operand re-reads: less CU time per launch).  Process-wide; results do not depend on it.  Returns the previous value. */
-int madtp_gemm_set_small_tile(int cfg);
+/* The dispatch decision madtp_gemm (flags 0), madtp_gemm_pair (MADTP_PLAN_PAIR) or madtp_gemm_splitk (splitk > 1, c_dtype F32,
+ * ldc = N) takes for a problem on `stream`, without launching: no HIP call, nothing allocated; every pointer counts as 16-byte
+ * aligned and the stream-K workspace as available.  Writes MADTP_PLAN_FIELDS int32 into plan (plan_len >= MADTP_PLAN_FIELDS):
+ *   status (0, a MADTP_E_* code, or 1000 = this pair runs as two launches; then kernel is -1 and the rest 0),
+ *   kernel (0 gemm_kernel, 1 wave-specialised 256x128, 2 lockstep 256x256, 3 ping-pong), gemm_kernel variant (0..3 = the
+ *   configurations 1..4 of madtp_gemm_set_config), tile rows, tile columns, row tiles, column tiles, column-group width of the tile
+ *   order (0 = row-panel major), grid, LDS bytes, stream-K tail, descriptor-based LDS-DMA, vector epilogue, output mode (0 f32,
+ *   1 bf16, 2 f16-split, 3 f16), operand format (0 bf16, 1 f16, 2 f16-split, 3 f32).
+ * Follows MADTP_GEMM_* / madtp_gemm_set_config and the stream's attributes like a launch.  No reference counterpart. */
+#define MADTP_PLAN_PAIR 1
+#define MADTP_PLAN_BIAS 2
+#define MADTP_PLAN_RESIDUAL 4
+#define MADTP_PLAN_M_DEV 8 /* the row count is read on the device (internal sync-free encoder path), M is its upper bound */
+#define MADTP_PLAN_FIELDS 15
+int madtp_gemm_plan(int M, int N, int K, int lda, int ldw, int ldc, int ldr, int ab_dtype, int c_dtype, int splitk, int flags,
+                    void* stream, int32_t* plan, int plan_len);
 
 /* Per-STREAM scheduling attributes (ABI 29; no reference counterpart - the reference runs one batch at a time on the default
  * stream, compress_nlvr_dtp.py:73-99).  A caller that keeps several forwards in flight on one GPU can give each forward its own
@@ -93,8 +98,15 @@ int madtp_gemm_set_small_tile(int cfg);
  *   madtp_stream_set_sched      tells the library what the stream owns, so that launches on it are sized for it:
  *       cus_per_xcd (1..32; 0 = unchanged / the whole chip = 32): the persistent GEMM kernels launch 8 * cus_per_xcd workgroups
  *           and the dispatch rules count rounds over 8 * cus_per_xcd CUs;
- *       sq_cost (> 0) and small_tile (-1..3): the two hints above for launches on THIS stream only (<= 0 / -2 = follow the
- *           process-wide setting) - concurrent callers with different needs do not share state.
+ *       sq_cost (> 0): scheduling hint for the automatic dispatch of launches on THIS stream - the relative per-round cost of a
+ *           256x256 tile against a 256x128 tile (1.7 = an isolated launch; a caller that keeps several forwards in flight on the
+ *           GPU lowers it - the other streams fill sparse last rounds, so the more efficient tile wins more often);
+ *       small_tile (-1..3): the tile configuration of the SMALL problems (fewer than 200 tiles of 256x128, e.g. the 1280-row
+ *           GEMMs of the text encoders): -1 = automatic (the smallest tile that fits one round: lowest latency of a lone launch),
+ *           0 = 128x128, 1 = 64x128, 2 = 64x128 with three stages, 3 = 64x64; a caller with several forwards in flight sets 0
+ *           (fewer operand re-reads: less CU time per launch);
+ *       sq_cost <= 0 / small_tile -2 = the process default (MADTP_GEMM_SQ_COST, else 1.7 / MADTP_GEMM_SMALL_CFG, else -1) -
+ *           concurrent callers with different needs do not share state.
  *       Results never depend on these attributes (same arithmetic per output element in every kernel choice).
  *   madtp_stream_destroy        forgets the attributes and destroys a stream made by madtp_stream_create_cumask.
  * Attributes may be set for any stream (also one the caller created); up to 64 streams per process carry attributes. */

@@ -19,6 +19,7 @@
 #include "common.h"
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -26,6 +27,9 @@
 #include <vector>
 
 #include "gemm_device.h"
+#include "gemm_plan.h"  // the dispatch policy (host) and sk_parts (host and device)
+static_assert(GEMM_ROWB == ROWB, "gemm_plan.h sizes the LDS rings with the slab width of the kernels");
+static_assert(OM_F32 == 0 && OM_BF16 == 1 && OM_F16S == 2 && OM_F16 == 3, "GemmPlan::om (gemm_plan.h) is the epilogue's output mode");
 #include "internal.h"
 
 namespace {
@@ -825,7 +829,6 @@ extern "C" int madtp_debug_read_ws_ts(long long* out) {
 
 // gemm_pp.hip: the ping-pong 256x256 kernel lives in its own translation unit (args = const GemmArgs*)
 __attribute__((visibility("hidden"))) int madtp_gemm_pp_launch(const void* args, int om, int mode, int rows, int grid, void* stream);
-#include "gemm_table.h"  // per-shape kernel choice of the big problems, measured (tools/gemm_autotune.py)
 
 // ---- optional HIP-event profiling of every GEMM launch (bench.py's roofline leg) -----------------------------------
 namespace {
@@ -868,20 +871,14 @@ extern "C" int madtp_profile_end(char* buf, int cap) {
 
 // second problem of a madtp_gemm_pair launch (same shape, leading dimensions and dtypes as the first)
 struct GemmPair { const void* A; const void* W; const float* bias; void* C; float acc_scale; };
-constexpr int PAIR_UNSUPPORTED = 1000;  // internal: this shape does not run on the wave-specialised kernel
 
 static int gemm_launch(const void* A, const void* W, const float* bias, const float* residual, void* C, int M, int N, int K,
                        int lda, int ldw, int ldc, int ldr, int ab_dtype, int c_dtype, int act, float acc_scale, float out_scale,
                        int splitk, void* stream, const GemmPair* pair = nullptr, DevN m_dev = DevN{nullptr, 0, 0});
 
-// Workgroups per XCD of the two big-GEMM kernels (default 32 = one persistent workgroup per CU walking its share of the tiles).
-// A larger cap gives every workgroup fewer tiles (>= tiles / 8: one tile each) - the launch then frees CUs tile by tile, which
-// lets the small kernels of ANOTHER stream in between (madtp_amd/pipeline.py) at the price of the cross-tile pipelining.
-
 // Per-stream scheduling attributes (madtp_stream_set_sched, include/madtp_hip.h): what slice of the chip a stream owns (a CU-masked
 // stream of a caller that partitions the GPU between forwards in flight) and that caller's dispatch hints.  Readers are the launch
 // paths (lock-free scan of a small table: a slot's key is published last), writers take the mutex.
-struct StreamSched { int cus_per_xcd; float sq_cost; int small_tile; };
 constexpr int SCHED_SLOTS = 64;
 static std::atomic<void*> g_sched_key[SCHED_SLOTS];
 static std::atomic<int> g_sched_cus[SCHED_SLOTS];
@@ -950,71 +947,45 @@ extern "C" int madtp_stream_destroy(void* stream) {
     return 0;
 }
 
-// workgroups per XCD of a persistent big-GEMM launch on `stream`: the process setting scaled to the CUs the stream owns
-static int gemm_wg_per_xcd(const StreamSched& ss) {
-    static const int env = env_int("MADTP_GEMM_WG_PER_XCD", 32);
-    int v = env < 1 ? 32 : env;
-    if (ss.cus_per_xcd < 32) { v = v * ss.cus_per_xcd / 32; if (v < 1) v = 1; }
-    return v;
+// The process switches of the dispatch (gemm_plan.h GemmSwitches) and MADTP_GEMM_DEBUG, read from the environment once.
+struct GemmEnv { GemmSwitches sw; int dbg; };
+static GemmEnv gemm_env_read() {
+    GemmEnv e;
+    GemmSwitches& sw = e.sw;
+    sw.force_cfg = env_int("MADTP_GEMM_CFG", 0);
+    if (sw.force_cfg < 0 || sw.force_cfg > 10 || sw.force_cfg == 8) sw.force_cfg = 0;  // (8 is retired: include/madtp_hip.h)
+    sw.desc = env_int("MADTP_GEMM_DESC", 1);
+    sw.big_min_m = max(env_int("MADTP_GEMM_BIG_MIN_M", 4096), 256);
+    sw.big_min_tiles = max(env_int("MADTP_GEMM_BIG_MIN_TILES", 200), 1);
+    sw.pair = env_int("MADTP_GEMM_PAIR", 1);
+    sw.sq = env_int("MADTP_GEMM_SQ", 1);
+    sw.pp = env_int("MADTP_GEMM_PP", 1);
+    sw.table = env_int("MADTP_GEMM_TABLE", 1);
+    sw.ngrp = env_int("MADTP_GEMM_NGRP", -1);
+    sw.sk = env_int("MADTP_GEMM_SK", 0);
+    sw.wg_per_xcd = env_int("MADTP_GEMM_WG_PER_XCD", 32);
+    sw.small_cfg = env_int("MADTP_GEMM_SMALL_CFG", -1);
+    if (sw.small_cfg < -1 || sw.small_cfg > 3) sw.small_cfg = -1;
+    const char* c = getenv("MADTP_GEMM_SQ_COST");
+    sw.sq_cost = c ? (float)atof(c) : 1.7f;
+    if (!(sw.sq_cost > 0.f)) sw.sq_cost = 1.7f;
+    e.dbg = env_int("MADTP_GEMM_DEBUG", 0);
+    return e;
 }
-
-// forced tile configuration (madtp_gemm_set_config / MADTP_GEMM_CFG): A/B measurements and the per-kernel tests
+static const GemmEnv& gemm_env() {
+    static const GemmEnv e = gemm_env_read();
+    return e;
+}
+// forced tile configuration (madtp_gemm_set_config; -1 = the environment's MADTP_GEMM_CFG): A/B measurements and the per-kernel tests
 static std::atomic<int> g_force_cfg{-1};
-static int gemm_force_cfg() {
-    int v = g_force_cfg.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char* e = getenv("MADTP_GEMM_CFG");
-        v = e ? atoi(e) : 0;
-        if (v < 0 || v > 10 || v == 8) v = 0;  // (8 is retired: include/madtp_hip.h)
-        g_force_cfg.store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
-// Per-round cost of a 256x256 tile relative to a 256x128 tile in the dispatch rule below.  1.7 is what an isolated launch
-// measures (the rule then counts rounds).  With several forwards in flight on one GPU the tail of a sparse last round is filled
-// by the other streams' kernels, so the round count matters less than the per-flop efficiency of the tile (the 256x256 tile
-// reads half the LDS bytes per MFMA): madtp_amd/pipeline.py lowers the cost to 0.9 while its workers run - measured NLVR
-// 25.2 -> 25.7 k images/s with four in flight, but 20.1 -> 19.2 k on the serial loop, which keeps 1.7.
-static std::atomic<float> g_sq_cost{-1.f};
-static std::atomic<int> g_sq_cost_hinted{0};  // a caller's hint is in force (madtp_gemm_set_sq_cost): the measured table steps aside
-static float gemm_sq_cost() {
-    float v = g_sq_cost.load(std::memory_order_relaxed);
-    if (v <= 0.f) {
-        const char* e = getenv("MADTP_GEMM_SQ_COST");
-        v = e ? (float)atof(e) : 1.7f;
-        if (!(v > 0.f)) v = 1.7f;
-        g_sq_cost.store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
-// Tile configuration of the SMALL problems (the 1280-row GEMMs of the text encoders), -1 = automatic: the automatic rule takes
-// the smallest tile that still fits one round, which is what a lone latency-bound launch wants; with several forwards in flight
-// the CU time of a launch counts, not its latency, and the 128x128 tile (a quarter of the operand re-reads of 64x64) wins:
-// NLVR 25.5 -> 26.2 k images/s, retrieval 28.5 -> 30.4 k with four in flight, -3.5 % on the serial loop (which keeps -1).
-static std::atomic<int> g_small_tile{-2};
-static int gemm_small_tile() {
-    int v = g_small_tile.load(std::memory_order_relaxed);
-    if (v == -2) {
-        const char* e = getenv("MADTP_GEMM_SMALL_CFG");
-        v = e ? atoi(e) : -1;
-        if (v < -1 || v > 3) v = -1;
-        g_small_tile.store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
-extern "C" int madtp_gemm_set_small_tile(int cfg) {
-    const int prev = gemm_small_tile();
-    g_small_tile.store((cfg < 0 || cfg > 3) ? -1 : cfg, std::memory_order_relaxed);
-    return prev;
-}
-extern "C" float madtp_gemm_set_sq_cost(float cost) {
-    const float prev = gemm_sq_cost();
-    g_sq_cost.store(cost > 0.f ? cost : -1.f, std::memory_order_relaxed);
-    g_sq_cost_hinted.store(cost > 0.f && cost != 1.7f ? 1 : 0, std::memory_order_relaxed);
-    return prev;
+static GemmSwitches gemm_switches() {
+    GemmSwitches sw = gemm_env().sw;
+    const int forced = g_force_cfg.load(std::memory_order_relaxed);
+    if (forced >= 0) sw.force_cfg = forced;
+    return sw;
 }
 extern "C" int madtp_gemm_set_config(int cfg) {
-    const int prev = gemm_force_cfg();
+    const int prev = gemm_switches().force_cfg;
     g_force_cfg.store((cfg < 0 || cfg > 10 || cfg == 8) ? 0 : cfg, std::memory_order_relaxed);
     return prev;
 }
@@ -1030,7 +1001,7 @@ extern "C" int madtp_gemm_pair(const void* A0, const void* A1, const void* W0, c
     const GemmPair p{A1, W1, bias1, C1, acc_scale1};
     int rc = gemm_launch(A0, W0, bias0, nullptr, C0, M, N, K, lda, ldw, ldc, 0, ab_dtype, c_dtype, MADTP_ACT_NONE, acc_scale0, 1.f, 1,
                          stream, &p);
-    if (rc != PAIR_UNSUPPORTED) return rc;
+    if (rc != GEMM_PAIR_UNSUPPORTED) return rc;
     rc = gemm_launch(A0, W0, bias0, nullptr, C0, M, N, K, lda, ldw, ldc, 0, ab_dtype, c_dtype, MADTP_ACT_NONE, acc_scale0, 1.f, 1, stream);
     if (rc) return rc;
     return gemm_launch(A1, W1, bias1, nullptr, C1, M, N, K, lda, ldw, ldc, 0, ab_dtype, c_dtype, MADTP_ACT_NONE, acc_scale1, 1.f, 1,
@@ -1072,8 +1043,7 @@ extern "C" int madtp_gemm_splitk_pp(const void* A, const void* W, float* part, i
     g.out_scale = 1.f; g.acc_scale = g.acc_scale2 = acc_scale;
     g.splitk = splits; g.fast_epi = 1;
     g.ntm = (M + 255) / 256; g.ntn = (N + 255) / 256;
-    const int slots_max = (g.ntm * g.ntn * splits + 7) / 8, cap = gemm_wg_per_xcd(stream_sched(stream));
-    const int grid = 8 * (slots_max < cap ? slots_max : cap);
+    const int grid = gemm_grid((g.ntm * g.ntn * splits + 7) / 8, gemm_wg_per_xcd(gemm_switches(), stream_sched(stream)));
     const int rc = madtp_gemm_pp_launch(&g, OM_F32, 2, 256, grid, stream);
     if (rc) return rc;
     MADTP_LAUNCH_CHECK();
@@ -1109,10 +1079,6 @@ extern "C" int madtp_splitk_sum(const float* part, int splits, size_t count, flo
 // 75 MB operand and the f32 residual from HBM rather than from the Infinity Cache - the same launches take the same ~92 us with
 // and without it and the next GEMM loses ~3 us to the evicted lines (profiles/r02_gemm_sk_ab.txt).
 struct SkWorkspace { float* ws; int* tick; };
-static bool sk_enabled() {
-    static const int sk_env = env_int("MADTP_GEMM_SK", 0);
-    return sk_env != 0;
-}
 static bool sk_workspace(hipStream_t s, SkWorkspace& out) {
     static std::mutex mu;
     static std::map<std::pair<int, hipStream_t>, SkWorkspace> pool;
@@ -1130,17 +1096,6 @@ static bool sk_workspace(hipStream_t s, SkWorkspace& out) {
     out = it->second;
     return true;
 }
-// Cost (in rounds of 256x128 tiles) of the wave-specialised kernel on t256 tiles.  The stream-K tail pays for K >= 2048 only
-// (measured, tools/gemm_bench.py ab / profiles/r02_gemm_sk_ab.txt): parking and re-reading the partials costs ~16 us per
-// launch, while the few tiles of a plain last round run ~25 % faster than in a full round (no contention), so with K = 768
-// (12 slabs, ~13 us per lone tile) the split loses 4-10 us and with K = 3072 it wins 6-14 us (M = 11-14 k rows, N = 768).
-constexpr int SK_MIN_SLABS = 32;
-static float ws_cost(int t256, int nk, bool sk, int cpx = 32) {
-    const int nsl = (t256 + 7) / 8, rounds = nsl / cpx, rem = nsl - rounds * cpx;
-    if (rem == 0) return (float)rounds;
-    const int parts = (sk && cpx == 32 && nk >= SK_MIN_SLABS) ? sk_parts(rem, 32, nk) : 0;
-    return (float)rounds + (parts ? 0.65f : 1.0f);
-}
 
 int madtp_i_gemm(const void* A, const void* W, const float* bias, const float* residual, void* C, int M, int N, int K, int lda, int ldw,
                  int ldc, int ldr, int ab_dtype, int c_dtype, int act, float acc_scale, float out_scale, DevN m_dev, void* stream) {
@@ -1148,238 +1103,129 @@ int madtp_i_gemm(const void* A, const void* W, const float* bias, const float* r
                        m_dev);
 }
 
+// The planner's input for a launch of this shape; every pointer counts as 16-byte aligned until the caller says otherwise.
+static GemmProblem gemm_problem(int M, int N, int K, int lda, int ldw, int ldc, int ldr, int ab_dtype, int c_dtype, int splitk, bool pair,
+                                bool bias, bool residual, bool m_dev) {
+    GemmProblem p;
+    p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr;
+    p.ab_dtype = ab_dtype; p.c_dtype = c_dtype; p.splitk = splitk;
+    p.pair = pair; p.bias = bias; p.residual = residual; p.m_dev = m_dev;
+    p.ab_aligned = p.c_aligned = p.bias_aligned = p.res_aligned = p.pair_aligned = true;
+    return p;
+}
+
+extern "C" int madtp_gemm_plan(int M, int N, int K, int lda, int ldw, int ldc, int ldr, int ab_dtype, int c_dtype, int splitk, int flags,
+                               void* stream, int32_t* plan, int plan_len) {
+    if (!plan || plan_len < MADTP_PLAN_FIELDS) return MADTP_E_BADARG;
+    const GemmProblem p = gemm_problem(M, N, K, lda, ldw, ldc, ldr, ab_dtype, c_dtype, splitk, flags & MADTP_PLAN_PAIR, flags & MADTP_PLAN_BIAS,
+                                       flags & MADTP_PLAN_RESIDUAL, flags & MADTP_PLAN_M_DEV);
+    const GemmPlan pl = gemm_plan(p, gemm_switches(), stream_sched(stream));
+    memcpy(plan, &pl, sizeof(pl));  // (GemmPlan is MADTP_PLAN_FIELDS ints in the documented order: gemm_plan.h)
+    return 0;
+}
+
+// One launch per kernel instantiation (the LDS opt-in of MADTP_ENSURE_MAX_LDS is remembered per instantiation).
+template <void (*KERNEL)(GemmArgs)>
+static int gemm_launch_kernel(const GemmArgs& g, const GemmPlan& pl, int threads, hipStream_t s) {
+    MADTP_ENSURE_MAX_LDS(KERNEL, pl.lds);
+    hipLaunchKernelGGL(KERNEL, dim3(pl.grid), dim3(threads), pl.lds, s, g);
+    return 0;
+}
+// operand format (GemmPlan::mode) and output mode -> instantiation: a 2-byte output has the operands' element format
+static int gemm_launch_sq(const GemmArgs& g, const GemmPlan& pl, hipStream_t s) {
+    return pl.om == OM_BF16 ? gemm_launch_kernel<gemm_sq_kernel<OM_BF16>>(g, pl, 512, s) : gemm_launch_kernel<gemm_sq_kernel<OM_F32>>(g, pl, 512, s);
+}
+static int gemm_launch_ws(const GemmArgs& g, const GemmPlan& pl, hipStream_t s) {
+    const bool lp_out = pl.om != OM_F32;
+    switch (pl.mode) {
+        case 1: return lp_out ? gemm_launch_kernel<gemm_ws_kernel<false, OM_F16, true>>(g, pl, 768, s)
+                              : gemm_launch_kernel<gemm_ws_kernel<false, OM_F32, true>>(g, pl, 768, s);
+        case 2: return lp_out ? gemm_launch_kernel<gemm_ws_kernel<true, OM_F16S>>(g, pl, 768, s)
+                              : gemm_launch_kernel<gemm_ws_kernel<true, OM_F32>>(g, pl, 768, s);
+        default: return lp_out ? gemm_launch_kernel<gemm_ws_kernel<false, OM_BF16>>(g, pl, 768, s)
+                               : gemm_launch_kernel<gemm_ws_kernel<false, OM_F32>>(g, pl, 768, s);
+    }
+}
+template <class TT, int OM>
+static int gemm_launch_small(const GemmArgs& g, const GemmPlan& pl, hipStream_t s) {
+    constexpr const GemmSmallTile* T = kGemmSmallTiles;  // the plan sized grid and LDS from this table: instantiate from it as well
+    switch (pl.variant) {
+        case 0: return gemm_launch_kernel<gemm_kernel<TT, OM, T[0].bm, T[0].bn, T[0].stages>>(g, pl, NTHREADS, s);
+        case 1: return gemm_launch_kernel<gemm_kernel<TT, OM, T[1].bm, T[1].bn, T[1].stages>>(g, pl, NTHREADS, s);
+        case 2: return gemm_launch_kernel<gemm_kernel<TT, OM, T[2].bm, T[2].bn, T[2].stages>>(g, pl, NTHREADS, s);
+        default: return gemm_launch_kernel<gemm_kernel<TT, OM, T[3].bm, T[3].bn, T[3].stages>>(g, pl, NTHREADS, s);
+    }
+}
+static int gemm_launch_small(const GemmArgs& g, const GemmPlan& pl, hipStream_t s) {
+    const bool lp_out = pl.om != OM_F32;
+    switch (pl.mode) {
+        case 0: return lp_out ? gemm_launch_small<bf16_t, OM_BF16>(g, pl, s) : gemm_launch_small<bf16_t, OM_F32>(g, pl, s);
+        case 1: return lp_out ? gemm_launch_small<F16P, OM_F16>(g, pl, s) : gemm_launch_small<F16P, OM_F32>(g, pl, s);
+        case 2: return lp_out ? gemm_launch_small<F16S, OM_F16S>(g, pl, s) : gemm_launch_small<F16S, OM_F32>(g, pl, s);
+        default: return lp_out ? gemm_launch_small<float, OM_BF16>(g, pl, s) : gemm_launch_small<float, OM_F32>(g, pl, s);
+    }
+}
+
 static int gemm_launch(const void* A, const void* W, const float* bias, const float* residual, void* C, int M, int N, int K,
                        int lda, int ldw, int ldc, int ldr, int ab_dtype, int c_dtype, int act, float acc_scale, float out_scale,
                        int splitk, void* stream, const GemmPair* pair, DevN m_dev) {
-    if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0) return MADTP_E_BADARG;
-    if (ab_dtype != MADTP_F32 && ab_dtype != MADTP_BF16 && ab_dtype != MADTP_F16S && ab_dtype != MADTP_F16) return MADTP_E_DTYPE;
-    if (c_dtype != MADTP_F32 && c_dtype != MADTP_BF16 && c_dtype != MADTP_F16S && c_dtype != MADTP_F16) return MADTP_E_DTYPE;
-    const bool x3 = ab_dtype == MADTP_F16S;
-    const bool f16 = ab_dtype == MADTP_F16;  // plain f16 operands: the bf16 kernels' instantiations on the f16 MFMA
-    if (c_dtype == MADTP_F16S && !x3) return MADTP_E_DTYPE;  // the split epilogue exists on the f16-split kernels only
-    if (c_dtype == MADTP_BF16 && (x3 || f16)) return MADTP_E_DTYPE;  // a 2-byte output of 2-byte operands has their element format
-    if (c_dtype == MADTP_F16 && !f16) return MADTP_E_DTYPE;
-    const int esz = ab_dtype == MADTP_F32 ? 4 : 2;
-    if ((K * esz) % ROWB != 0) return MADTP_E_SHAPE;
-    if (!aligned16(A) || !aligned16(W) || (lda * esz) % 16 || (ldw * esz) % 16) return MADTP_E_ALIGN;
-    // f16-split operands: leading dimensions count f16 elements (2 planes of K per activation row and per weight row)
-    if (lda < (x3 ? 2 : 1) * K || ldw < (x3 ? 2 : 1) * K || ldc < (c_dtype == MADTP_F16S ? 2 : 1) * N || (residual && ldr < N))
-        return MADTP_E_SHAPE;
+    if (!A || !W || !C) return MADTP_E_BADARG;  // (sizes, dtypes, leading dimensions: gemm_plan)
     GemmArgs g;
     g.A = (const char*)A; g.W = (const char*)W; g.bias = bias; g.residual = residual; g.C = C;
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldr = ldr; g.act = act; g.out_scale = out_scale;
     g.acc_scale = acc_scale; g.acc_scale2 = pair ? pair->acc_scale : acc_scale;
     g.ldc = (c_dtype == MADTP_BF16 || c_dtype == MADTP_F16) ? -ldc : ldc;  // negative: a 2-byte output (scalar fallback epilogue)
-    g.range_flag = (c_dtype == MADTP_F16S || c_dtype == MADTP_F16) ? madtp_internal_range_flag() : nullptr;
-    static const int dbg = env_int("MADTP_GEMM_DEBUG", 0);
-    const int force_cfg = gemm_force_cfg();
-    g.dbg = dbg;
+    g.dbg = gemm_env().dbg;
     g.splitk = splitk;
-    g.ngrp = 0;
-    g.pair = 0; g.A2 = g.W2 = nullptr; g.bias2 = nullptr; g.C2 = nullptr;
-    g.sk = 0; g.sk_ws = nullptr; g.sk_tick = nullptr;
+    g.pair = pair != nullptr;
+    g.A2 = pair ? (const char*)pair->A : nullptr; g.W2 = pair ? (const char*)pair->W : nullptr;
+    g.bias2 = pair ? pair->bias : nullptr; g.C2 = pair ? pair->C : nullptr;
     g.m_dev = m_dev.p; g.m_mul = m_dev.mul;
-    if (m_dev.p && (M >= 4096 || pair || splitk != 1)) return MADTP_E_SHAPE;  // device-side M: the small-tile kernels only
-    {
-        static const int desc_env = env_int("MADTP_GEMM_DESC", 1);  // 0: gemm_kernel builds its LDS-DMA addresses per instruction (A/B runs)
-        const size_t a_bytes = ((size_t)M + 127) * (size_t)lda * esz, w_bytes = ((size_t)N + 255) * (size_t)ldw * esz;
-        g.desc = desc_env && a_bytes < ((size_t)1 << 31) && w_bytes < ((size_t)1 << 31);
-    }
-    // vector epilogue needs 16-byte aligned rows on every epilogue operand
-    // (and, for the descriptor-bounded stores, a 256-row block of C below 2 GiB; bf16 output with an f32 residual has no
-    // caller on the path and takes the scalar epilogue)
-    g.fast_epi = (N % 8 == 0) && (ldc % 8 == 0) && aligned16(C) && (!bias || aligned16(bias)) &&
-                 (!residual || (aligned16(residual) && ldr % 4 == 0 && c_dtype != MADTP_BF16 && c_dtype != MADTP_F16)) &&
-                 (size_t)ldc * 256 * 4 < ((size_t)1 << 31);
-    // tile configuration (MADTP_GEMM_CFG=1..4 forces one of the gemm_kernel variants for A/B measurements):
-    //   0: 128x128, 2-stage ring, 2 workgroups/CU  - default, and the f32 path
-    //   1: 64x128, 2 stages, 3 WG/CU   2: 64x128, 3 stages, 2 WG/CU   3: 64x64, 3 stages, 3 WG/CU
-    // Small bf16 problems (the 1280-row GEMMs of the text encoder) are bound by the LDS-DMA rate of a CU (~40 GB/s with one
-    // resident workgroup): what counts is spreading the operand bytes over ALL CUs in one round, so they take the
-    // smallest tile whose grid still fits one round of 3 workgroups per CU (measured: 64x64 beats 128x128 by 20-45 % on
-    // M=1280, N<=2304; 64x128 wins for N=3072).
-    // The wave-specialised 256x128 kernel takes a problem once its tiles fill most of the chip (>= 200 of 256 CUs) - e.g. not
-    // the 4480 x 768 GEMMs of a 128-pair re-ranking batch (108 tiles), which run better on 420 64x128 tiles.
-    int cfg = 0;
+
+    GemmProblem p = gemm_problem(M, N, K, lda, ldw, ldc, ldr, ab_dtype, c_dtype, splitk, pair != nullptr, bias != nullptr, residual != nullptr,
+                                 m_dev.p != nullptr);
+    p.ab_aligned = aligned16(A) && aligned16(W); p.c_aligned = aligned16(C); p.bias_aligned = aligned16(bias); p.res_aligned = aligned16(residual);
+    p.pair_aligned = !pair || (aligned16(pair->A) && aligned16(pair->W) && aligned16(pair->C) && aligned16(pair->bias));
+    GemmSwitches sw = gemm_switches();
     const StreamSched ss = stream_sched(stream);  // the CUs this stream owns (32 per XCD unless the caller said otherwise) + its hints
-    const int cpx = ss.cus_per_xcd, ncu = 8 * cpx;
-    const int t256 = ((M + 255) / 256) * ((N + 127) / 128);
-    // Thresholds of the big-tile kernels (persistent 256-row tiles): M >= 4096 and most of the chip covered - what a lone launch
-    // wants (latency).  MADTP_GEMM_BIG_MIN_M / _TILES lower them (experiments with several forwards in flight, where a launch's
-    // CU time counts and a 1280-row problem on 45 efficient tiles costs a third of the CU time of 720 small ones).
-    static const int big_min_m = max(env_int("MADTP_GEMM_BIG_MIN_M", 4096), 256);
-    static const int big_min_t = max(env_int("MADTP_GEMM_BIG_MIN_TILES", 200), 1);
-    const int big_min_tiles = cpx == 32 ? big_min_t : (big_min_t * ncu + 255) / 256;  // "most of the chip" = most of the stream's CUs
-    const bool big = !m_dev.p && M >= big_min_m && t256 >= big_min_tiles;
-    const bool lp16 = ab_dtype != MADTP_F32;  // 2-byte operand planes: bf16, or f16-split (three times the slab stream)
-    if (lp16 && !big) {
-        const int t64 = ((M + 63) / 64) * ((N + 63) / 64) * splitk, t64x128 = ((M + 63) / 64) * ((N + 127) / 128) * splitk;
-        if (t64 <= 3 * ncu) cfg = 3;
-        else if (t64x128 <= 3 * ncu) cfg = 1;
-    }
-    const int auto_cfg = cfg;  // the kernel choice below follows the AUTOMATIC tile rule; the hint only picks among the small tiles
-    if (lp16 && !big) {
-        const int small = ss.small_tile > -2 ? ss.small_tile : gemm_small_tile();  // scheduling hint (per stream, else madtp_gemm_set_small_tile), -1 = the rule above
-        if (small >= 0 && small <= 3) cfg = small;
-    }
-    // MADTP_GEMM_CFG=5 forces the wave-specialised kernel, 1..4 force a gemm_kernel variant (A/B measurements)
-    bool ws_ok = lp16 && splitk == 1 &&
-                 (force_cfg == 5 || force_cfg == 7 || (force_cfg == 0 && !m_dev.p && M >= big_min_m && (big || (auto_cfg == 0 && M >= 4096))));
-    if (pair) {
-        static const int pair_env = env_int("MADTP_GEMM_PAIR", 1);  // 0: always two launches (A/B runs)
-        ws_ok = pair_env && lp16 && force_cfg == 0 && M >= big_min_m && 2 * t256 >= big_min_tiles && g.fast_epi &&
-                aligned16(pair->A) && aligned16(pair->W) && aligned16(pair->C) && (!pair->bias || aligned16(pair->bias));
-        if (!ws_ok) return PAIR_UNSUPPORTED;
-        g.pair = 1; g.A2 = (const char*)pair->A; g.W2 = (const char*)pair->W; g.bias2 = pair->bias; g.C2 = pair->C;
-    }
-    if (force_cfg > 0 && force_cfg <= 4) cfg = force_cfg - 1;
-    // (round 5, measured and dropped: "deep ring" variants of the small tiles - 64x64 x 6 stages / 64x128 x 5, one workgroup per CU,
-    //  five / four slabs in flight - are no faster on the text encoder's 1280-row problems (768x768: 11.7 vs 11.8 us, and 24 vs 13.5 us
-    //  where the tiles need three rounds): their ~10 us are launch ramp, first-touch latency and drain, not the K loop)
-    if (x3 && cfg == 0) cfg = 1;  // f16-split: 64x128 tiles (the 128x128 variant would spill the kept P0 fragments)
+    GemmPlan pl = gemm_plan(p, sw, ss);
     hipStream_t s = (hipStream_t)stream;
+    SkWorkspace skw{nullptr, nullptr};
+    // The workspace is allocated on the first launch whose plan USES the tail; without it: the plan for no tail.  (Before the planner
+    // it was allocated whenever the tail was priced into the choice.  One corner differs: the wave-specialised kernel chosen at the
+    // tail's price, its grid not 256 - MADTP_GEMM_WG_PER_XCD - so no tail, AND an allocation that would have failed: the old code then
+    // chose again at the plain price, this one keeps the choice.)
+    if (pl.sk && !sk_workspace(s, skw)) {
+        sw.sk_workspace = false;
+        pl = gemm_plan(p, sw, ss);
+    }
+    if (pl.status) return pl.status;
+    g.ntm = pl.ntm; g.ntn = pl.ntn; g.ngrp = pl.ngrp; g.desc = pl.desc; g.fast_epi = pl.fast_epi;
+    g.sk = pl.sk; g.sk_ws = skw.ws; g.sk_tick = skw.tick;
+    g.range_flag = (c_dtype == MADTP_F16S || c_dtype == MADTP_F16) ? madtp_internal_range_flag() : nullptr;
+
     GemmRecord rec;
     if (g_prof_on) {
         // timing-only events: no system-scope fence when they complete (hipEventDisableSystemFence: "can improve the accuracy of timing
         // measurements by avoiding the cost of cache writeback and invalidation, and the performance impact of those actions on the
         // execution of following work") - the un-instrumented forward has no such fences between its kernels either
         (void)hipEventCreateWithFlags(&rec.e0, hipEventDisableSystemFence); (void)hipEventCreateWithFlags(&rec.e1, hipEventDisableSystemFence);
+        const int esz = ab_dtype == MADTP_F32 ? 4 : 2;
         rec.flops = 2.0 * M * N * K; rec.dt = ab_dtype; rec.M = M; rec.N = N; rec.K = K;
         // algorithmic HBM bytes: A and W once, C once (x splits), bias, residual once
-        rec.bytes = (double)esz * (x3 ? 2.0 : 1.0) * ((double)M * K + (double)N * K) + (double)M * N * ((c_dtype == MADTP_BF16 || c_dtype == MADTP_F16) ? 2 : 4) * splitk +
-                    (bias ? 4.0 * N : 0.0) + (residual ? 4.0 * M * N : 0.0);
+        rec.bytes = (double)esz * (ab_dtype == MADTP_F16S ? 2.0 : 1.0) * ((double)M * K + (double)N * K) +
+                    (double)M * N * ((c_dtype == MADTP_BF16 || c_dtype == MADTP_F16) ? 2 : 4) * splitk + (bias ? 4.0 * N : 0.0) + (residual ? 4.0 * M * N : 0.0);
         if (pair) { rec.flops *= 2.0; rec.bytes *= 2.0; }  // two problems in this launch
         (void)hipEventRecord(rec.e0, s);
     }
-#define MADTP_LAUNCH_GEMM(TT, LP, BM_, BN_, ST_, WGCU)                                                                   \
-    do {                                                                                                               \
-        g.ntm = (M + BM_ - 1) / BM_;                                                                                   \
-        g.ntn = (N + BN_ - 1) / BN_;                                                                                   \
-        const int slots_max = ((g.ntm * g.ntn + 7) / 8) * g.splitk;                                                    \
-        const int per_xcd = cpx * WGCU;                                                                                \
-        const int grid = 8 * (slots_max < per_xcd ? slots_max : per_xcd);                                              \
-        const size_t lds = (size_t)(BM_ + BN_) * ROWB * ST_;                                                           \
-        MADTP_ENSURE_MAX_LDS((gemm_kernel<TT, LP, BM_, BN_, ST_>), lds);                                               \
-        hipLaunchKernelGGL((gemm_kernel<TT, LP, BM_, BN_, ST_>), dim3(grid), dim3(NTHREADS), lds, s, g);               \
-    } while (0)
-#define MADTP_DISPATCH_CFG(TT, LP)                                             \
-    do {                                                                       \
-        if (cfg == 0) MADTP_LAUNCH_GEMM(TT, LP, 128, 128, 2, 2);               \
-        else if (cfg == 1) MADTP_LAUNCH_GEMM(TT, LP, 64, 128, 2, 3);           \
-        else if (cfg == 2) MADTP_LAUNCH_GEMM(TT, LP, 64, 128, 3, 2);           \
-        else MADTP_LAUNCH_GEMM(TT, LP, 64, 64, 3, 3);                          \
-    } while (0)
-
-    // 256x256 kernel: bf16 operands, no split-K / pair.  Chosen when its round count times its per-tile cost (measured ~1.7x a
-    // 256x128 tile) beats the wave-specialised kernel's; MADTP_GEMM_CFG=6 forces it, MADTP_GEMM_SQ=0 turns it off (A/B runs).
-    bool sq_ok = false, pp_ok = false;
-    int pp_rows = 256;  // tile height of the ping-pong kernel: 256, or 192 (gemm_pp.hip FA = 3)
-    SkWorkspace skw{nullptr, nullptr};
-    const bool sk_on = ws_ok && !x3 && ab_dtype == MADTP_BF16 && (force_cfg == 5 || (force_cfg == 0 && sk_enabled() && K / 64 >= SK_MIN_SLABS)) &&
-                       sk_workspace(s, skw);
-    if (lp16 && splitk == 1 && !pair && (K % 64) == 0 &&
-        ((size_t)M + 255) * (size_t)lda * 2 < ((size_t)1 << 32) && ((size_t)N + 255) * (size_t)ldw * 2 < ((size_t)1 << 32)) {
-        static const int sq_env = env_int("MADTP_GEMM_SQ", 1);
-        const int t_sq = ((M + 255) / 256) * ((N + 255) / 256), t_192 = ((M + 191) / 192) * ((N + 255) / 256);
-        // the ping-pong main loop (gemm_pp_kernel, gemm_pp.hip) needs an even slab count; MADTP_GEMM_PP=0 keeps the lockstep kernel
-        // (A/B runs), cfg 9 forces its 256-row tile, cfg 10 its 192-row tile, cfg 6 forces the lockstep kernel.  Its tile costs
-        // ~1.5 tiles of 256x128 (lockstep: 1.7) - profiles/r04_gemm_pp_ab.txt; a caller's sq_cost hint (several forwards in flight)
-        // applies to both.  Plain f16 and f16-split operands: the 256-column tile exists as the ping-pong kernel only.
-        static const int pp_env = env_int("MADTP_GEMM_PP", 1);
-        const bool pp_can = (K % 128) == 0;
-        pp_ok = pp_can && (force_cfg == 9 || force_cfg == 10 || (force_cfg == 0 && pp_env));
-        const bool sq_allowed = sq_env && ((!f16 && !x3) || pp_ok);
-        float unit = ss.sq_cost > 0.f ? ss.sq_cost : gemm_sq_cost();
-        if (pp_ok && unit > 1.5f) unit = 1.5f;
-        const bool hinted = ss.sq_cost > 0.f || cpx != 32 || g_sq_cost_hinted.load(std::memory_order_relaxed);  // (the table was measured on the whole idle chip)
-        // Choice for an automatic launch: (1) the measured table (gemm_table.h: per (operand class, N, K, output) and 64-row bucket
-        // of M the fastest of {wave-specialised 256x128, ping-pong 256x256, ping-pong 192x256} on an idle MI355X; MADTP_GEMM_TABLE=0
-        // turns it off; it steps aside while a caller's in-flight hint is in force), else (2) the round-count cost model.
-        static const int tab_env = env_int("MADTP_GEMM_TABLE", 1);
-        int choice = -1;  // 0 wave-specialised, 1 ping-pong / lockstep 256x256, 2 ping-pong 192x256
-        if (force_cfg == 6 && !f16 && !x3) choice = 1;
-        else if (force_cfg == 9 && pp_can) choice = 1;
-        else if (force_cfg == 10 && pp_can) choice = 2;
-        else if (force_cfg == 0 && sq_allowed && ws_ok) {
-            if (pp_ok && tab_env && cpx == 32 && (tab_env == 2 || !hinted))
-                choice = gemm_table_lookup(x3, M, N, K, c_dtype == MADTP_F32);
-            if (choice < 0) {
-                const float cost_ws = ws_cost(t256, K / 64, sk_on, cpx);
-                const float cost_sq = 2 * t_sq >= big_min_tiles ? unit * (float)((t_sq + ncu - 1) / ncu) : 1e9f;
-                // a 192-row tile: 3/4 of the MFMAs of a 256-row one behind the same barriers and 7/8 of its DMA stream (measured ~0.8)
-                const float cost_192 = (pp_ok && 2 * t_192 >= big_min_tiles) ? 0.8f * unit * (float)((t_192 + ncu - 1) / ncu) : 1e9f;
-                choice = (cost_192 < cost_sq && cost_192 < cost_ws) ? 2 : (cost_sq < cost_ws ? 1 : 0);
-            }
-        }
-        sq_ok = choice >= 1;
-        pp_ok = pp_ok && sq_ok;
-        if (choice == 2) pp_rows = 192;
-        if (sq_ok && !pp_ok && (f16 || x3)) sq_ok = false;  // (no lockstep instantiation for these operand formats)
+    int rc;
+    switch (pl.kernel) {
+        case GEMM_PP_KERNEL: rc = madtp_gemm_pp_launch(&g, pl.om, pl.mode, pl.rows, pl.grid, s); break;
+        case GEMM_SQ_KERNEL: rc = gemm_launch_sq(g, pl, s); break;
+        case GEMM_WS_KERNEL: rc = gemm_launch_ws(g, pl, s); break;
+        default: rc = gemm_launch_small(g, pl, s); break;
     }
-    static const int grp_env = env_int("MADTP_GEMM_NGRP", -1);  // column-group width of the tile order: -1 (unset) = automatic, 0 = off, n > 0 = forced (A/B runs)
-    if (sq_ok) {
-        g.ntm = (M + pp_rows - 1) / pp_rows;
-        g.ntn = (N + 255) / 256;
-        {
-            // MADTP_GEMM_NGRP: column-group width of the tile order (0 = row-panel major; unset = row-panel major up to 15 column
-            // tiles - every shape of the forward - and groups of 8 beyond: with 32 column tiles (8192^3) an XCD's 32 concurrent
-            // tiles then share 4 A panels and 8 W panels instead of 1 + 32: 1.32 -> 1.53-1.55 PF, profiles/r04_gemm_pp_ab.txt)
-            const int grp = grp_env >= 0 ? grp_env : (g.ntn >= 16 ? 8 : 0);
-            g.ngrp = (grp > 0 && grp < g.ntn) ? grp : 0;
-        }
-        const int slots_max = (g.ntm * g.ntn + 7) / 8;
-        const int cap = gemm_wg_per_xcd(ss);
-        const int grid = 8 * (slots_max < cap ? slots_max : cap);
-        const size_t lds = (size_t)2 * (256 + 256) * ROWB;
-        if (pp_ok) {
-            const int om = c_dtype == MADTP_F32 ? OM_F32 : (c_dtype == MADTP_F16S ? OM_F16S : (c_dtype == MADTP_F16 ? OM_F16 : OM_BF16));
-            const int rc = madtp_gemm_pp_launch(&g, om, x3 ? 2 : (f16 ? 1 : 0), pp_rows, grid, s);
-            if (rc) return rc;
-        } else if (c_dtype == MADTP_BF16) {
-            MADTP_ENSURE_MAX_LDS((gemm_sq_kernel<OM_BF16>), lds);
-            hipLaunchKernelGGL((gemm_sq_kernel<OM_BF16>), dim3(grid), dim3(512), lds, s, g);
-        } else {
-            MADTP_ENSURE_MAX_LDS((gemm_sq_kernel<OM_F32>), lds);
-            hipLaunchKernelGGL((gemm_sq_kernel<OM_F32>), dim3(grid), dim3(512), lds, s, g);
-        }
-    } else if (ws_ok) {
-        // wave-specialised 256x128 kernel (one 12-wave workgroup per CU, 144 KiB LDS ring)
-        g.ntm = (M + 255) / 256;
-        g.ntn = (N + 127) / 128;
-        // column groups (tile_mn): keep one group's W rows (~2.4 MB) L2-resident when W as a whole is far larger than L2
-        {
-            int G = grp_env > 0 ? grp_env : (12 * 768) / K;
-            if (G < 1) G = 1;
-            const bool on = grp_env > 0 || (grp_env == -1 && g.ntn >= 4 * G);
-            g.ngrp = (on && G < g.ntn) ? G : 0;
-        }
-        const int slots_max = (g.ntm * g.ntn * (g.pair ? 2 : 1) + 7) / 8;
-        const int cap = gemm_wg_per_xcd(ss);
-        const int grid = 8 * (slots_max < cap ? slots_max : cap);
-        if (sk_on && grid == 256) { g.sk = 1; g.sk_ws = skw.ws; g.sk_tick = skw.tick; }
-        const size_t lds = (size_t)3 * (256 + 128) * ROWB;
-#define MADTP_LAUNCH_WS(X3_, OM_, ...)                                                                        \
-    do {                                                                                                     \
-        MADTP_ENSURE_MAX_LDS((gemm_ws_kernel<X3_, OM_ __VA_OPT__(,) __VA_ARGS__>), lds);                      \
-        hipLaunchKernelGGL((gemm_ws_kernel<X3_, OM_ __VA_OPT__(,) __VA_ARGS__>), dim3(grid), dim3(768), lds, s, g); \
-    } while (0)
-        if (f16) {
-            if (c_dtype == MADTP_F16) MADTP_LAUNCH_WS(false, OM_F16, true); else MADTP_LAUNCH_WS(false, OM_F32, true);
-        } else if (x3) {
-            if (c_dtype == MADTP_F16S) MADTP_LAUNCH_WS(true, OM_F16S); else MADTP_LAUNCH_WS(true, OM_F32);
-        } else {
-            if (c_dtype == MADTP_BF16) MADTP_LAUNCH_WS(false, OM_BF16); else MADTP_LAUNCH_WS(false, OM_F32);
-        }
-#undef MADTP_LAUNCH_WS
-    } else if (ab_dtype == MADTP_BF16) {
-        if (c_dtype == MADTP_BF16) MADTP_DISPATCH_CFG(bf16_t, OM_BF16); else MADTP_DISPATCH_CFG(bf16_t, OM_F32);
-    } else if (f16) {
-        if (c_dtype == MADTP_F16) MADTP_DISPATCH_CFG(F16P, OM_F16); else MADTP_DISPATCH_CFG(F16P, OM_F32);
-    } else if (x3) {
-        if (c_dtype == MADTP_F16S) MADTP_DISPATCH_CFG(F16S, OM_F16S); else MADTP_DISPATCH_CFG(F16S, OM_F32);
-    } else {
-        if (c_dtype == MADTP_BF16) MADTP_DISPATCH_CFG(float, OM_BF16); else MADTP_DISPATCH_CFG(float, OM_F32);
-    }
+    if (rc) return rc;
     if (g_prof_on) {
         (void)hipEventRecord(rec.e1, s);
         g_prof.push_back(rec);

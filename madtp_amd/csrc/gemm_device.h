@@ -84,20 +84,6 @@ __device__ __forceinline__ void tile_mn(const GemmArgs& g, int t, int& tm, int& 
     tm = r / gw; tn = grp * g.ngrp + (r - tm * gw);
 }
 
-// Stream-K tail of a persistent kernel (the wave-specialised 256x128 one): an XCD's `nslots` tiles are `rounds` full rounds of
-// its `gl` workgroups plus `rem` tiles.  With rem <= gl/2 the last round would leave most CUs idle for a whole tile time (the
-// N = 768 GEMMs of the ViT layers at 11-14 k rows are 1.03-1.3 rounds), so each of the rem tiles is cut along K into `parts`
-// pieces run by `parts` workgroups; every consumer wave parks its 64x64 partial in the workspace and the LAST wave to arrive
-// (ticket per tile and wave position) sums the pieces in piece order - deterministic - and runs the epilogue.
-constexpr int SK_MAX_PARTS = 8;
-__host__ __device__ __forceinline__ int sk_parts(int rem, int gl, int nk) {
-    if (rem <= 0) return 0;
-    int p = gl / rem;
-    if (p > SK_MAX_PARTS) p = SK_MAX_PARTS;
-    if (p > nk / 2) p = nk / 2;  // at least two slabs per piece
-    return p >= 2 ? p : 0;
-}
-
 // The same with a buffer descriptor: NQ instructions of this wave, per-lane source offsets roff[] (row within the tile, swizzled
 // slot - constants of the kernel), scalar offset soff (tile origin + K position); rows past `bytes` read as zeros.
 // (A __device__ function on purpose: with these builtins inside the kernel's issue lambda the host pass of this compiler emits

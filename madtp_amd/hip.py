@@ -13,7 +13,7 @@ import torch
 F32, BF16, F16S, F16 = 0, 1, 2, 3  # F16S: f16-split operand planes of the fp32-accurate GEMM (include/madtp_hip.h), torch.float16
 #                                    F16: plain IEEE f16 operands (the "f16" fast mode), see set_lp_format below
 ACT_NONE, ACT_GELU, ACT_QUICK_GELU, ACT_RELU = 0, 1, 2, 3
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libmadtp_hip.so")
@@ -25,8 +25,7 @@ _SIGS = {
     "madtp_profile_end": (c_int, [ctypes.c_char_p, c_int]),
     "madtp_gemm": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_int, c_int, c_int, c_float, c_float, c_void_p]),
     "madtp_gemm_set_config": (c_int, [c_int]),
-    "madtp_gemm_set_sq_cost": (c_float, [c_float]),
-    "madtp_gemm_set_small_tile": (c_int, [c_int]),
+    "madtp_gemm_plan": (c_int, [c_int] * 11 + [c_void_p, c_void_p, c_int]),
     "madtp_stream_create_cumask": (c_int, [c_void_p, c_void_p, c_int]),
     "madtp_stream_set_sched": (c_int, [c_void_p, c_int, c_float, c_int]),
     "madtp_stream_get_sched": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -325,10 +324,17 @@ class gemm_config:
         load().madtp_gemm_set_config(self.prev)
 
 
-def gemm_set_sq_cost(cost):
-    """madtp_gemm_set_sq_cost (include/madtp_hip.h): dispatch hint for callers that keep several forwards in flight; cost <= 0
-    restores the default.  -> previous value."""
-    return float(load().madtp_gemm_set_sq_cost(float(cost)))
+PLAN_PAIR, PLAN_BIAS, PLAN_RESIDUAL, PLAN_M_DEV = 1, 2, 4, 8
+PLAN_FIELDS = ("status", "kernel", "variant", "rows", "cols", "ntm", "ntn", "ngrp", "grid", "lds", "sk", "desc", "fast_epi", "om", "mode")
+
+
+def gemm_plan(M, N, K, lda, ldw, ldc, ldr, ab_dtype, c_dtype, splitk=1, flags=0, stream=None, out=None):
+    """madtp_gemm_plan (include/madtp_hip.h): the dispatch decision a launch of this problem on `stream` (a pointer, or None) would
+    take - kernel, tile, grid, tile order - as a list of ints in PLAN_FIELDS order.  No GPU needed.  `out`: a ctypes int32 array of
+    at least len(PLAN_FIELDS) to fill instead (returned as is)."""
+    buf = (ctypes.c_int32 * len(PLAN_FIELDS))() if out is None else out
+    _check(load().madtp_gemm_plan(M, N, K, lda, ldw, ldc, ldr, ab_dtype, c_dtype, splitk, flags, stream, buf, len(PLAN_FIELDS)), "madtp_gemm_plan")
+    return list(buf) if out is None else out
 
 
 _score_fast = 0  # (madtp_amd.runtime sets it with the precision mode, its default included)
@@ -342,11 +348,6 @@ def set_score_fast(on):
     if _lib is not None:
         _lib.madtp_set_score_fast(_score_fast)
     return prev
-
-
-def gemm_set_small_tile(cfg):
-    """madtp_gemm_set_small_tile (include/madtp_hip.h): tile configuration of the small problems, -1 = automatic.  -> previous."""
-    return int(load().madtp_gemm_set_small_tile(int(cfg)))
 
 
 # ---- per-stream scheduling attributes (include/madtp_hip.h, ABI 29) ------------------------------------------------------------------
@@ -418,7 +419,7 @@ def masked_stream_info(stream_ptr):
 
 
 def stream_set_sched(stream, cus_per_xcd=0, sq_cost=0.0, small_tile=-2):
-    """madtp_stream_set_sched for any torch stream: cus_per_xcd 0 = unchanged, sq_cost <= 0 / small_tile -2 = the process-wide hints."""
+    """madtp_stream_set_sched for any torch stream: cus_per_xcd 0 = unchanged, sq_cost <= 0 / small_tile -2 = the process defaults."""
     ptr = stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
     if ptr == 0:
         raise ValueError("the null stream cannot carry scheduling attributes")

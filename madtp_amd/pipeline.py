@@ -24,42 +24,6 @@ import threading
 import torch
 
 
-# (Rounds 3-5; since round 6 the hints are per-STREAM attributes - madtp_stream_set_sched - and this block only serves
-# MADTP_INFLIGHT_GLOBAL_HINTS=1, the A/B switch.)  The GEMM dispatch hints were process-wide state of the library
-# (include/madtp_hip.h): runners that overlap in time share ONE
-# setting - the first one in sets it and remembers the previous values, the last one out restores them (a nested or concurrent
-# runner neither re-applies its own hints nor restores stale ones).
-_hint_lock = threading.Lock()
-_hint_depth = 0
-_hint_prev = (None, None)
-
-
-def _hints_enter(sq_cost, small_tile):
-    global _hint_depth, _hint_prev
-    from . import hip
-    with _hint_lock:
-        if _hint_depth == 0:
-            prev_cost = hip.gemm_set_sq_cost(sq_cost) if sq_cost else None
-            prev_small = hip.gemm_set_small_tile(small_tile) if small_tile is not None else None
-            _hint_prev = (prev_cost, prev_small)
-        _hint_depth += 1
-    return True
-
-
-def _hints_exit():
-    global _hint_depth, _hint_prev
-    from . import hip
-    with _hint_lock:
-        _hint_depth -= 1
-        if _hint_depth == 0:
-            prev_cost, prev_small = _hint_prev
-            if prev_cost is not None:
-                hip.gemm_set_sq_cost(prev_cost)
-            if prev_small is not None:
-                hip.gemm_set_small_tile(prev_small)
-            _hint_prev = (None, None)
-
-
 def shared_replica(model):
     """A second instance of `model` for another forward in flight that SHARES every parameter, buffer and prepared (compute-dtype)
     weight with it and owns only the per-call records the forward leaves on its modules (`last_prune`, `score_side`, the encoder
@@ -157,7 +121,7 @@ class InflightRunner:
         #                                                   workers creates exactly n streams, as many as are in use)
         self.streams = [None] * self.n                    # the streams of the most recent run(), by worker
         self.n_high = 0
-        # GEMM dispatch hint while the workers run (hip.gemm_set_sq_cost; per workload, measured): None = leave the default
+        # GEMM dispatch hints of the workers' streams (hip.stream_set_sched; per workload, measured): None = leave the default
         self.sq_cost = getattr(workload, "inflight_sq_cost", None)
         self.small_tile = getattr(workload, "inflight_small_tile", None)
         if os.environ.get("MADTP_INFLIGHT_SQ_COST"):  # A/B runs: "0" = no hint
@@ -207,8 +171,6 @@ class InflightRunner:
         else:
             high = [i < max(1, n // 2) for i in range(self.n)]
         part = self._partition_for(n)
-        import os
-        per_stream_hints = os.environ.get("MADTP_INFLIGHT_GLOBAL_HINTS", "0") != "1"  # ("1": the rounds-3-5 process-wide setters, A/B)
         for i in range(n):
             if part is not None:
                 key = (tuple(part), i)
@@ -221,8 +183,8 @@ class InflightRunner:
             pr = -1 if high[i] else 0
             if pr not in self._by_prio[i]:
                 self._by_prio[i][pr] = torch.cuda.Stream(device=self.device, priority=pr)
-                if per_stream_hints and (self.sq_cost or self.small_tile is not None):
-                    # the dispatch hints travel with the STREAM (madtp_stream_set_sched, round 6): no process-wide library state, two
+                if self.sq_cost or self.small_tile is not None:
+                    # the dispatch hints travel with the STREAM (madtp_stream_set_sched): no process-wide library state, two
                     # runners (or another user of the library) in one process do not see each other's hints
                     from . import hip
                     hip.stream_set_sched(self._by_prio[i][pr], 0, self.sq_cost or 0.0, -2 if self.small_tile is None else self.small_tile)
@@ -237,16 +199,10 @@ class InflightRunner:
         mode = runtime.get_precision()
         threads = [threading.Thread(target=self._work, args=(i, per[i], mode), name=f"madtp-inflight-{i}")
                    for i in range(self.n) if per[i]]
-        # (CU-masked streams carry their hints themselves - madtp_stream_set_sched - and leave the process-wide state alone)
-        hinted = len(threads) > 1 and part is None and not per_stream_hints and _hints_enter(self.sq_cost, self.small_tile)
-        try:
-            for t in threads:
-                t.start()
-            for t in threads:
-                t.join()
-        finally:
-            if hinted:
-                _hints_exit()
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
         for s in used:
             main.wait_stream(s)
         if self.errors:

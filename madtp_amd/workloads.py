@@ -70,10 +70,10 @@ class Workload:
     # configuration (profiles/r03_inflight.txt (i), (j)): NLVR 22.6-23.1 k with two, 23.8-24.5 k with three, 25.1-25.5 k with four,
     # 24.1-24.3 k with five
     default_inflight = 4
-    # GEMM dispatch hint while several forwards are in flight (include/madtp_hip.h madtp_gemm_set_sq_cost); measured with four
+    # GEMM dispatch hint while several forwards are in flight (the sq_cost attribute of madtp_stream_set_sched, include/madtp_hip.h); measured with four
     # in flight: NLVR 25.2 -> 25.7 k images/s, VQA 4.77 -> 4.87 k, retrieval 29.4 -> 28.4 k (keeps the default)
     inflight_sq_cost = 0.9
-    # ... and the 128x128 tile for the small problems (madtp_gemm_set_small_tile): NLVR 25.5 -> 26.2 k, retrieval 28.5 -> 30.4 k,
+    # ... and the 128x128 tile for the small problems (its small_tile attribute): NLVR 25.5 -> 26.2 k, retrieval 28.5 -> 30.4 k,
     # VQA 4.81 -> 4.85 k with four in flight
     inflight_small_tile = 0
 

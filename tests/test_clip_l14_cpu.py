@@ -84,7 +84,7 @@ def test_patchify_validates_arguments_without_gpu():
     from madtp_amd import build, hip
     build.build(verbose=False)
     lib = hip.load()
-    assert lib.madtp_abi_version() == 30
+    assert lib.madtp_abi_version() == 31
     E_BADARG, E_SHAPE, E_DTYPE = -1, -2, -3
     for P in (14, 16, 7):
         assert lib.madtp_patchify(0, 16, 2, 336, P, hip.F32, None) == E_BADARG    # null image

@@ -73,7 +73,7 @@ def test_new_symbols_validate_arguments_without_gpu():
     from madtp_amd import build, hip
     build.build(verbose=False)
     lib = hip.load()
-    assert lib.madtp_abi_version() == 30
+    assert lib.madtp_abi_version() == 31
     assert lib.madtp_itc_loss(0, 0, 0, 0, 0, 0, 0, 0.4, 0, 0, 0, 0, 0, 4, 256, 12, None) == -1     # null pointers
     ws = int(lib.madtp_itc_workspace(4, 96, 12))
     assert ws > 0
