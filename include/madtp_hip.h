@@ -750,6 +750,22 @@ int madtp_itm_negatives(const float* image_feat, const float* text_feat, const f
                         const int64_t* idx, const int64_t* idx_world, const float* temp, const float* u, int64_t* neg, int* flag,
                         int B, int Bw, int D, void* stream);
 
+/* ---- CLIP's text embedding under autograd: clip/model.py:486-488 (csrc/clip.hip) ----------------------------------------------
+ * madtp_clip_embed: x[b,l,:] = table[ids[b,l],:] + pos[l,:] in one pass (token_embedding(text) + positional_embedding).
+ * ids int64 [B,L]; table f32 [V,D]; pos f32 [>=L,D]; x f32 [B,L,D]; D % 4 == 0.  The host checks the sizes only; like
+ * madtp_bert_embed the kernel reads the caller's ids as they are (every id must lie in [0,V)) and clamps nothing. */
+int madtp_clip_embed(const int64_t* ids, const float* table, const float* pos, float* x, int B, int L, int D, int V, void* stream);
+/* madtp_embedding_grad: the gradient of table[ids] with respect to the table (torch's zeros_like(table).index_add_(0, ids, dx)):
+ *   dtable[v,:] = sum over the positions i (flat b*L + l) with ids[i] == v of dx[i,:], added in ascending i in f32.
+ * ids int64 [n]; dx f32 [n,D]; dtable f32 [V,D].  Every row of dtable is written by this call - rows whose id does not occur as
+ * exact zeros - so dtable needs no initialisation; no atomics: identical calls give identical bits.  An id outside [0,V) has
+ * no row and contributes nothing.  ws: device workspace of madtp_embedding_grad_workspace(n) bytes, 8-byte aligned (the ids
+ * in sorted order and their positions; the query returns 0 for an n outside the supported range).
+ * 1 <= n <= 256 * 77, D % 64 == 0, D <= 1024, any V >= 1. */
+size_t madtp_embedding_grad_workspace(int n);
+int madtp_embedding_grad(const int64_t* ids, const float* dx, float* dtable, void* ws, size_t ws_bytes, int n, int D, int V,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1389,3 +1389,53 @@ def clip_vision_forward_with_grad(vt, img, space_dict, temperature, max_keep):
     if vt.proj is not None:
         cls = LinearFunction.apply(cls, vt.proj.t().contiguous(), None, hip.ACT_NONE)  # x @ proj (:311-312)
     return cls, sd_all
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# CLIP's text tower (clip/model.py:485-503) under autograd: token + positional embedding, the causal blocks (they route themselves
+# to VitBlockFunction / QueryModelFunction with max_keep = eot.max() + 2), the EOT rows, ln_final, x @ text_projection.
+
+class ClipTextEmbedFunction(torch.autograd.Function):
+    """x = token_embedding.weight[ids] + positional_embedding[:L] (clip/model.py:486-488, madtp_clip_embed).  The table's gradient
+    is the ordered segmented sum of madtp_embedding_grad (no atomics: the same bits in every run, absent rows written as zeros by
+    the same launches); the positional gradient is the column sum over the batch, as in EmbeddingsFunction."""
+
+    @staticmethod
+    def forward(ctx, ids, table, pos):
+        ids = ids.contiguous()
+        ctx.save_for_backward(ids)
+        ctx.table_shape, ctx.pos_rows = tuple(table.shape), pos.shape[0]
+        return hip.clip_embed(ids, table.detach().contiguous(), pos.detach().contiguous())
+
+    @staticmethod
+    def backward(ctx, dx):
+        (ids,) = ctx.saved_tensors
+        B, L = ids.shape
+        V, D = ctx.table_shape
+        with torch.no_grad():
+            dx = dx.contiguous().float()
+            dtable = hip.embedding_grad(ids.view(-1), dx.view(B * L, D), V) if ctx.needs_input_grad[1] else None
+            dpos = None
+            if ctx.needs_input_grad[2]:
+                dpos = colsum(dx.view(B, L * D)).view(L, D)
+                if L < ctx.pos_rows:
+                    full = dx.new_zeros(ctx.pos_rows, D)
+                    full[:L] = dpos
+                    dpos = full
+        return None, dtable, dpos
+
+
+def clip_text_forward_with_grad(model, text, space_dict, temperature):
+    """CLIP.encode_text under autograd -> (features [B, embed_dim], sd_txt_ft_all); fp32 / f16x3 mode.  Everything the backward
+    reads lives in the Functions' contexts, so a later no-grad call of the same blocks (the reference's encode_text_m runs the
+    STUDENT transformer, clip/model.py:516) leaves this graph intact."""
+    _check_mode("the CLIP text backward")
+    B = text.shape[0]
+    x = ClipTextEmbedFunction.apply(text, model.token_embedding.weight, model.positional_embedding)
+    eot = text.argmax(dim=-1)
+    max_keep = eot.max() + 2  # :492
+    xs, _, _, sd_all, _ = model.transformer(x.permute(1, 0, 2), space_dict, temperature, None, max_keep)
+    xb = xs.permute(1, 0, 2)
+    rows = xb[torch.arange(B, device=xb.device), eot].contiguous()  # :501 (LayerNorm is row-wise: gather first)
+    rows = LayerNormFunction.apply(rows, model.ln_final.weight, model.ln_final.bias, model.ln_final.eps)  # :497
+    return LinearFunction.apply(rows, model.text_projection.t().contiguous(), None, hip.ACT_NONE), sd_all  # x @ text_projection

@@ -14,6 +14,7 @@ order="reference" is pinned to the reference fixture.
 from collections import OrderedDict
 
 import torch
+import torch.nn.functional as F
 from torch import nn
 
 from . import hip
@@ -204,13 +205,18 @@ class VisionTransformer(nn.Module):
 
 
 class CLIP(nn.Module):
-    """clip/model.py:316-503, evaluation side: the towers, embeddings and projections with the reference's parameter names
-    (checkpoints load by key; the momentum copies `*_m` and the queues of :395-436 are training state and are not created -
-    load_state_dict(strict=False), as build_model :715 does, skips them), encode_image :482-483 and encode_text :485-503."""
+    """clip/model.py:316-652: the towers, embeddings and projections with the reference's parameter names (checkpoints load by
+    key), encode_image :482-483 and encode_text :485-503.
+
+    evaluate=True is the evaluation model: the momentum copies `*_m` and the queues of :395-437 are not created
+    (load_state_dict(strict=False), as build_model :715 does, skips them) and forward() raises.  evaluate=False adds the
+    reference's training state under its names - visual_m, transformer_m, token_embedding_m, ln_final_m, text_projection_m,
+    positional_embedding_m, image_queue, text_queue, idx_queue, ptr_queue - and forward() is the contrastive training step of
+    :529-595 (see CLIP.forward).  queue_size: the reference hard-codes 57600 (:430); a keyword here, as in BLIP_Retrieval."""
 
     def __init__(self, embed_dim: int, image_resolution: int, vision_layers, vision_width: int, vision_patch_size: int,
                  context_length: int, vocab_size: int, transformer_width: int, transformer_heads: int,
-                 transformer_layers: int, evaluate: bool = True, config=None):
+                 transformer_layers: int, evaluate: bool = True, config=None, queue_size: int = 57600):
         super().__init__()
         self.context_length = context_length
         self.sd_num = 100 if config is None else config['sd_num']
@@ -232,8 +238,34 @@ class CLIP(nn.Module):
         self.tokenize = None
         self.vision_layers, self.transformer_layers = vision_layers, transformer_layers
         self._cache = PreparedCache()
-        if not evaluate:
-            self.initialize_parameters()
+        self.evaluate = evaluate
+        if evaluate:
+            return
+        self.initialize_parameters()
+        # the training state of :347, :395-437, the reference's names and order
+        self.criterion = nn.CosineEmbeddingLoss()
+        self.momentum = 0.995
+        self.visual_m = VisionTransformer(input_resolution=image_resolution, patch_size=vision_patch_size, width=vision_width,
+                                          layers=vision_layers, heads=vision_width // 64, output_dim=embed_dim, sd_dim=self.sd_dim)
+        self.transformer_m = Transformer(width=transformer_width, layers=transformer_layers, heads=transformer_heads,
+                                         attn_mask=self.build_attention_mask(), sd_dim=self.sd_dim)
+        self.token_embedding_m = nn.Embedding(vocab_size, transformer_width)
+        self.ln_final_m = LayerNorm(transformer_width)
+        self.model_pairs = [[self.visual, self.visual_m], [self.transformer, self.transformer_m],
+                            [self.token_embedding, self.token_embedding_m], [self.ln_final, self.ln_final_m]]
+        self.text_projection_m = nn.Parameter(torch.empty(transformer_width, embed_dim))
+        self.positional_embedding_m = nn.Parameter(torch.empty(self.context_length, transformer_width))
+        self.params_pairs = [[self.text_projection, self.text_projection_m],
+                             [self.positional_embedding, self.positional_embedding_m]]
+        self.copy_params()
+        self.queue_size = queue_size
+        self.register_buffer("image_queue", F.normalize(torch.randn(embed_dim, queue_size), dim=0))
+        self.register_buffer("text_queue", F.normalize(torch.randn(embed_dim, queue_size), dim=0))
+        self.register_buffer("idx_queue", torch.full((1, queue_size), -100))
+        self.register_buffer("ptr_queue", torch.zeros(1, dtype=torch.long))
+        self._ema = hip.EmaTable()
+        self._ema_pairs = None  # [(param_m, param)] of momentum_pairs(), built at the first update
+        self._ptr_host = None   # host mirror of ptr_queue: (value, ptr_queue._version it was read / written at)
 
     def initialize_parameters(self):
         """clip/model.py:438-464."""
@@ -281,10 +313,164 @@ class CLIP(nn.Module):
                              lambda: prepare_linear([self.text_projection.t()], None, cdt))
         return hip.gemm(to_compute(rows), pj.w, None, out_dtype=torch.float32, n=pj.n), sd_txt_ft_all
 
+    # ---- training state (evaluate=False): clip/model.py:505-652 ----
+    def encode_image_m(self, image, space_dict=None, temperature=0):
+        return self.visual_m(image, space_dict=space_dict, temperature=temperature)  # :505-506
+
+    def encode_text_m(self, text, space_dict=None, temperature=0):
+        """:508-526 as written: token_embedding_m, positional_embedding_m and text_projection_m around the STUDENT's
+        self.transformer and self.ln_final (:516, :520) - transformer_m and ln_final_m follow the EMA and never run."""
+        require_gpu(text, "text")
+        B = text.shape[0]
+        x = hip.clip_embed(text.contiguous(), self.token_embedding_m.weight.detach(), self.positional_embedding_m.detach())  # :509-511
+        eot = text.argmax(dim=-1)
+        max_keep = eot.max() + 2  # :515
+        xs, _, _, sd_txt_ft_all, _ = self.transformer(x.permute(1, 0, 2), space_dict, temperature, None, max_keep)  # :516
+        xb = as_f32_contig(xs.permute(1, 0, 2))
+        rows = xb[torch.arange(B, device=xb.device), eot].contiguous()  # :524
+        rows, _ = hip.layernorm(rows, self.ln_final.weight, self.ln_final.bias, self.ln_final.eps)  # :520
+        cdt = compute_dtype()
+        pj = self._cache.get(("text_projection_m", cdt), [self.text_projection_m],
+                             lambda: prepare_linear([self.text_projection_m.t()], None, cdt))
+        return hip.gemm(to_compute(rows), pj.w, None, out_dtype=torch.float32, n=pj.n), sd_txt_ft_all
+
+    @staticmethod
+    def _remove_alpha(model):
+        return [param for name, param in model.named_parameters() if 'alpha' not in name]
+
+    def momentum_pairs(self):
+        """[(param, param_m)] of :621-643: the module pairs by position after dropping names containing 'alpha', then the two
+        bare parameter pairs."""
+        pairs = [(p, pm) for a, m in self.model_pairs for p, pm in zip(self._remove_alpha(a), m.parameters())]
+        return pairs + [(p, pm) for p, pm in self.params_pairs]
+
+    @torch.no_grad()
+    def copy_params(self):  # :620-632
+        for p, pm in self.momentum_pairs():
+            pm.data.copy_(p.data)
+            pm.requires_grad = False
+
+    @torch.no_grad()
+    def _momentum_update(self):
+        """:634-643 p_m = p_m m + p (1 - m) for every pair, the two bare parameters included, in one launch (madtp_ema_update),
+        in place; the update epoch of every momentum parameter is bumped so that prepared weights follow (runtime.PreparedCache)."""
+        if self._ema_pairs is None:
+            self._ema_pairs = [(pm, p) for p, pm in self.momentum_pairs()]
+        self._ema.update(self._ema_pairs, self.momentum)
+        for pm, _ in self._ema_pairs:
+            pm._madtp_steps = getattr(pm, "_madtp_steps", 0) + 1
+
+    @torch.no_grad()
+    def _dequeue_and_enqueue(self, image_feat, text_feat, idxs):
+        """:598-618 with the pointer mirrored on the host (no int(ptr_queue) sync once it is known)."""
+        from .blip_retrieval import _all_gather
+        image_feats, text_feats = _all_gather(image_feat), _all_gather(text_feat)
+        n = image_feats.shape[0]
+        if self._ptr_host is None or self._ptr_host[1] != self.ptr_queue._version:
+            self._ptr_host = (int(self.ptr_queue[0]), self.ptr_queue._version)
+        ptr = self._ptr_host[0]
+        assert self.queue_size % n == 0  # for simplicity (:607)
+        if ptr % n != 0:
+            ptr = (ptr // n) * n
+        self.image_queue[:, ptr:ptr + n] = image_feats.T
+        self.text_queue[:, ptr:ptr + n] = text_feats.T
+        self.idx_queue[:, ptr:ptr + n] = idxs.view(1, -1)
+        ptr = (ptr + n) % self.queue_size
+        self.ptr_queue.fill_(ptr)
+        self._ptr_host = (ptr, self.ptr_queue._version)
+
+    @torch.no_grad()
+    def reset_queue(self):  # :645-652
+        dev = self.image_queue.device
+        self.image_queue = F.normalize(torch.randn(self.embed_dim, self.queue_size), dim=0).to(dev)
+        self.text_queue = F.normalize(torch.randn(self.embed_dim, self.queue_size), dim=0).to(dev)
+        self.idx_queue = torch.full((1, self.queue_size), -100).to(dev)
+        self.ptr_queue = torch.zeros(1, dtype=torch.long).to(dev)
+        self._ptr_host = None
+
+    def _fdt(self, sd_img_ft, sd_txt_ft):  # :578-584
+        si = sd_img_ft / (sd_img_ft.norm(dim=-1, keepdim=True) + 1e-10)
+        st = sd_txt_ft / (sd_txt_ft.norm(dim=-1, keepdim=True) + 1e-10)
+        si, st = si.reshape(-1, self.sd_dim), st.reshape(-1, self.sd_dim)
+        labels = torch.ones(si.shape[0], device=st.device).long()
+        return self.criterion(si, st, labels)
+
+    def forward(self, image, caption, alpha, idx, temperature=0):
+        """The training step of clip/model.py:529-595 -> (loss_ita, loss_fdt, loss_fdt_m).  evaluate=False models only.
+
+        caption: raw strings with model.tokenize set (as the reference's driver does), or an int tensor [B, context] of token ids,
+        passed through.  idx: int [B] image ids.  Student towers on the autograd routes of the HIP path
+        (backward.clip_vision_forward_with_grad / clip_text_forward_with_grad); then, under no_grad, the EMA (madtp_ema_update)
+        and the momentum pass on the inference kernels - the reference as written: encode_text_m runs the student's transformer
+        and ln_final a second time.  ITC: madtp_itc_loss per direction against [in-batch momentum features | queue] at
+        temp = exp(-logit_scale) formed on the device, BEFORE the queues advance (the gradient is formed there); the STUDENT
+        features are what the reference enqueues (:572).  temperature = 0: loss_fdt and loss_fdt_m are loss_ita itself.
+        With a process group the features and ids are gathered for the queue (blip_retrieval._all_gather).
+        Needs runtime.precision('fp32') or 'f16x3' (with runtime.training_f16x3()); embed_dim <= 512 (madtp_itc_loss)."""
+        if self.evaluate:
+            raise NotImplementedError("CLIP(evaluate=True) is the evaluation model (encode_image / encode_text): build it with "
+                                      "evaluate=False to train")
+        from .backward import _check_mode, clip_text_forward_with_grad
+        from .blip_retrieval import _ItcLoss, _all_gather, _dist_world
+        _check_mode("CLIP.forward (training)")
+        require_gpu(image, "image")
+        dev = image.device
+        with torch.no_grad():
+            self.logit_scale.clamp_(0, 4.6052)  # :530-531
+        B = image.size(0)
+        world = _dist_world()
+        if self.queue_size % (world * B) != 0:  # :607 (checked on the host, before any state moves)
+            raise AssertionError(f"queue_size {self.queue_size} is not a multiple of the gathered batch {world * B}")
+        idx = idx.to(device=dev, dtype=torch.int64).view(-1).contiguous()
+        sd = self.space_dict
+
+        image_features, sd_img_ft = self.encode_image(image, space_dict=sd, temperature=temperature)  # :537
+        if torch.is_tensor(caption) and not caption.is_floating_point():
+            text = caption.to(device=dev, dtype=torch.int64)
+        elif self.tokenize is not None:
+            text = self.tokenize(caption).to(device=dev, dtype=torch.int64)  # :538
+        else:
+            raise TypeError("caption must be an int tensor [B, context] of token ids, or model.tokenize must be set")
+        text = text.contiguous()
+        if torch.is_grad_enabled():
+            text_features, sd_txt_ft = clip_text_forward_with_grad(self, text, sd, temperature)  # :539
+        else:
+            text_features, sd_txt_ft = self.encode_text(text, space_dict=sd, temperature=temperature)
+        image_features = image_features / image_features.norm(dim=1, keepdim=True)  # :542-543
+        text_features = text_features / text_features.norm(dim=1, keepdim=True)
+        temp = torch.exp(-self.logit_scale)  # s = q k / temp = exp(logit_scale) q k (:545, :563-564)
+
+        with torch.no_grad():  # :547-552 momentum features (the EMA first)
+            self._momentum_update()
+            image_features_m, sd_img_ft_m = self.encode_image_m(image, space_dict=sd, temperature=temperature)
+            text_features_m, sd_txt_ft_m = self.encode_text_m(text, space_dict=sd, temperature=temperature)
+            image_features_m = (image_features_m / image_features_m.norm(dim=1, keepdim=True)).contiguous()
+            text_features_m = (text_features_m / text_features_m.norm(dim=1, keepdim=True)).contiguous()
+
+        # :533-536, :553-569 ITC against [in-batch momentum features | queue] (the queue as it is BEFORE this step's enqueue)
+        idx_q = self.idx_queue[0]
+        loss_i2t = _ItcLoss.apply(image_features, temp, image_features_m, text_features_m, self.text_queue, idx, idx_q, float(alpha))
+        loss_t2i = _ItcLoss.apply(text_features, temp, text_features_m, image_features_m, self.image_queue, idx, idx_q, float(alpha))
+        loss_ita = (loss_i2t + loss_t2i) / 2
+
+        idxs = _all_gather(idx)  # :571-572
+        self._dequeue_and_enqueue(image_features.detach(), text_features.detach(), idxs)
+
+        loss_fdt = loss_ita
+        loss_fdt_m = loss_ita
+        if temperature != 0 and sd_img_ft is not None and sd_txt_ft is not None:  # :576-584
+            loss_fdt = self._fdt(sd_img_ft, sd_txt_ft)
+        if temperature != 0 and sd_img_ft_m is not None and sd_txt_ft_m is not None:  # :586-593
+            with torch.no_grad():
+                loss_fdt_m = self._fdt(sd_img_ft_m, sd_txt_ft_m)
+        return loss_ita, loss_fdt, loss_fdt_m
+
 
 def build_model(state_dict: dict, evaluate: bool = False, config=None):
     """clip/model.py:678-716: geometry inferred from the checkpoint's tensor shapes (ViT towers), strict=False load.  The
-    reference casts weights to fp16 (convert_weights :653-675) and back to fp32 (clip/clip.py:148); here they stay fp32."""
+    reference casts weights to fp16 (convert_weights :653-675) and back to fp32 (clip/clip.py:148); here they stay fp32.
+    evaluate=False (the reference's default, and what the driver's training model is built with) gives the model with the
+    momentum copies and queues; as in the reference they are not re-copied after the load - the driver's checkpoints carry them."""
     if "visual.proj" not in state_dict:
         raise NotImplementedError("ResNet CLIP checkpoints are off the pruned ViT path")
     vision_width = state_dict["visual.conv1.weight"].shape[0]

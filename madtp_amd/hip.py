@@ -123,6 +123,10 @@ _SIGS = {
     "madtp_ema_blocks": (c_int, [ctypes.c_int64]),
     "madtp_ema_update": (c_int, [c_void_p, c_int, c_int, c_float, c_float, c_void_p]),
     "madtp_itm_negatives": (c_int, [c_void_p] * 10 + [c_int, c_int, c_int, c_void_p]),
+    # CLIP's text embedding under autograd (csrc/clip.hip)
+    "madtp_clip_embed": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p]),
+    "madtp_embedding_grad_workspace": (c_size_t, [c_int]),
+    "madtp_embedding_grad": (c_int, [c_void_p] * 4 + [c_size_t, c_int, c_int, c_int, c_void_p]),
     "madtp_token_gather_bwd": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p]),
     "madtp_token_score_bwd": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4
                               + [c_int, c_int, c_int, c_void_p]),
@@ -1527,3 +1531,40 @@ def itm_negatives(image_feat, text_feat, image_feat_world, text_feat_world, idx,
     _check(load().madtp_itm_negatives(_p(image_feat), _p(text_feat), _p(image_feat_world), _p(text_feat_world), _p(idx), _p(idx_world),
                                       _p(temp), _p(u), _p(neg), _p(flag), B, Bw, D, _stream()), "madtp_itm_negatives")
     return neg
+
+
+# ---- CLIP's text embedding under autograd (include/madtp_hip.h madtp_clip_embed / madtp_embedding_grad) ------------------------
+def clip_embed(ids, table, pos):
+    """x[b,l,:] = table[ids[b,l],:] + pos[l,:] (madtp_clip_embed): ids int64 [B,L]; table f32 [V,D]; pos f32 [>=L,D] -> f32 [B,L,D]."""
+    _gpu_i64(ids, "clip_embed: ids")
+    _gpu_f32(table, "clip_embed: table", 2)
+    _gpu_f32(pos, "clip_embed: pos", 2)
+    if ids.dim() != 2 or pos.shape[1] != table.shape[1] or pos.shape[0] < ids.shape[1]:
+        raise RuntimeError("clip_embed: ids must be [B,L], pos [>=L,D] and table [V,D]")
+    B, L = ids.shape
+    V, D = table.shape
+    x = torch.empty(B, L, D, dtype=torch.float32, device=table.device)
+    _check(load().madtp_clip_embed(_p(ids), _p(table), _p(pos), _p(x), B, L, D, V, _stream()), "madtp_clip_embed")
+    return x
+
+
+def embedding_grad(ids, dx, V, out=None):
+    """dtable [V,D] of table[ids] for the output gradient dx f32 [n,D] (ids int64, n elements): the sum over every id's
+    occurrences in ascending position, absent rows exact zeros (madtp_embedding_grad - no atomics, no memset).  out: an f32
+    [V,D] tensor to write (its contents do not matter)."""
+    _gpu_i64(ids, "embedding_grad: ids")
+    _gpu_f32(dx, "embedding_grad: dx", 2)
+    n, D = dx.shape
+    if ids.numel() != n:
+        raise RuntimeError("embedding_grad: ids and dx disagree")
+    if out is None:
+        out = torch.empty(V, D, dtype=torch.float32, device=dx.device)
+    else:
+        _gpu_f32(out, "embedding_grad: out", 2)
+        if out.shape != (V, D):
+            raise RuntimeError("embedding_grad: out must be [V,D]")
+    lib = load()
+    ws_bytes = int(lib.madtp_embedding_grad_workspace(n))
+    ws = torch.empty(max(ws_bytes, 8) // 8 + 1, dtype=torch.int64, device=dx.device)
+    _check(lib.madtp_embedding_grad(_p(ids), _p(dx), _p(out), _p(ws), ws.numel() * 8, n, D, V, _stream()), "madtp_embedding_grad")
+    return out

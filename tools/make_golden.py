@@ -1314,6 +1314,118 @@ def retr_train_case(name, B, size, L, temperature, idx, alpha, queue_size, seed=
           f"losses2={rec['losses2'].round(5).tolist()} neg={rec['neg'].tolist()} {n} gradients")
 
 
+class CanonicalTap(GatherTap):
+    """GatherTap that also puts the kept `indices` of each Reduce_token (the first vector_gather of a block call, the unsorted
+    torch.topk of clip/model.py:224) in ascending token order - the canonical order of the HIP path; the
+    reference's own order is implementation-defined and, in the causal text tower, visible in the values."""
+
+    def __call__(self, vectors, indices):
+        if self.tag is not None and vectors.shape[-1] > 1 and self.calls == 0:
+            indices = indices.sort(dim=-1).values
+        return super().__call__(vectors, indices)
+
+
+def clip_train_tokens(lens, seed):
+    """[B,77] CLIP token rows with exactly lens[b] word ids each (synth.synth_clip_tokens, one row per call)."""
+    return torch.cat([synth.synth_clip_tokens(1, 77, 100 * seed + b, n, n) for b, n in enumerate(lens)], 0)
+
+
+def clip_train_case(name, B, temperature, idx, cap_lens, alpha=0.4, queue_size=48, seed=0, size=96, nsample=32, lr=0.05):
+    """The reference's OWN CLIP training step (clip/model.py:529-595, CLIP(evaluate=False), model.eval()) at world 1 on the
+    ViT-B/16 geometry at 96^2 (37 tokens) with the 12-layer text tower: student towers, EMA, momentum pass (encode_text_m runs
+    the STUDENT transformer, :516), ITC against a small seeded queue, dequeue-and-enqueue of the student features;
+    loss = loss_ita + 0.1 loss_fdt + 0.1 loss_fdt_m as compress_retrieval_clip_dtp.py does.  For this recording only the kept
+    tokens of every pruning step are put in ascending order (CanonicalTap).  Then torch.optim.SGD(lr) steps on the gradients and a
+    SECOND forward is recorded (its losses only)."""
+    import clip.mock  # noqa: F401
+    import clip.model as cm
+    from madtp_amd import specs
+    cm.concat_all_gather = lambda t: t  # world 1
+    torch.manual_seed(seed)
+    model = cm.CLIP(512, size, 12, 768, 16, 77, 49408, 512, 8, 12, False, None)
+    model.eval()
+    sd = specs.synth_weights(specs.clip_shapes(size), seed)
+    sd["logit_scale"] = torch.tensor(2.6592600369327779)  # log(1 / 0.07), the reference's initial value (:387)
+    msg = model.load_state_dict(sd, strict=False)
+    assert not msg.unexpected_keys, msg.unexpected_keys
+    assert all(k.endswith("_m") or "_m." in k or "queue" in k for k in msg.missing_keys), msg.missing_keys[:8]
+    g = torch.Generator().manual_seed(1000 + seed)
+    model.queue_size = queue_size
+    iq = torch.full((1, queue_size), -100, dtype=torch.long)
+    iq[0, 1] = idx[-1]                     # an id of the batch already in the queue
+    iq[0, queue_size // 2] = 11
+    init = {"image_queue": torch.nn.functional.normalize(torch.randn(512, queue_size, generator=g), dim=0),
+            "text_queue": torch.nn.functional.normalize(torch.randn(512, queue_size, generator=g), dim=0),
+            "idx_queue": iq, "ptr_queue": torch.tensor([B + 1], dtype=torch.long)}  # (an unaligned pointer: rounded down, :609-610)
+    for k, v in init.items():
+        setattr(model, k, v.clone())
+    model.copy_params()
+    keys = sorted(model.state_dict().keys())
+    momentum = {id(p) for _, m in model.model_pairs for p in m.parameters()} | {id(pm) for _, pm in model.params_pairs}
+    images = synth.synth_images(B, size, seed)
+    text = clip_train_tokens(cap_lens, seed)
+    model.tokenize = lambda caption: text
+    idx_t = torch.tensor(idx, dtype=torch.long)
+    tap = CanonicalTap(cm)
+    lens = {"vit": [], "txt": [], "vit_m": []}
+    hooks = []
+    for tag, blocks in (("vit", model.visual.transformer.resblocks), ("txt", model.transformer.resblocks),
+                        ("vit_m", model.visual_m.transformer.resblocks)):
+        for i, blk in enumerate(blocks):
+            hooks.append(blk.register_forward_pre_hook(lambda m, a, t=tag, i=i: tap.set_tag(f"{t}{i}")))
+            hooks.append(blk.register_forward_hook(lambda m, a, o, t=tag: lens[t].append(o[0].shape[0])))
+    for p_ in model.parameters():
+        if id(p_) not in momentum:
+            p_.requires_grad_(True)
+        p_.grad = None
+    losses = model(images, ["caption"] * B, alpha, idx_t, temperature=temperature)
+    n_lens = {t: len(v) for t, v in lens.items()}
+    (losses[0] + 0.1 * losses[1] + 0.1 * losses[2]).backward()
+    rec = {"kind": "clip_train", "B": B, "size": size, "temperature": np.float64(temperature), "seed": seed, "nsample": nsample,
+           "alpha": np.float64(alpha), "idx": np.array(idx), "queue_size": queue_size, "lr": np.float64(lr),
+           "momentum": np.float64(model.momentum), "state_dict_keys": np.array(keys), "text": text.numpy(),
+           "cap_lens": np.array(cap_lens), "eot_pos": text.argmax(-1).numpy(), "init_logit_scale": np.float64(sd["logit_scale"].item()),
+           "init_image_queue": init["image_queue"].numpy(), "init_text_queue": init["text_queue"].numpy(),
+           "init_idx_queue": init["idx_queue"].numpy(), "init_ptr": int(init["ptr_queue"][0]),
+           "losses": np.array([float(x) for x in losses], dtype=np.float64),
+           "idx_queue": model.idx_queue.numpy().copy(), "ptr": int(model.ptr_queue[0]),
+           "vit_lens": np.array(lens["vit"]), "vit_m_lens": np.array(lens["vit_m"]),
+           "txt_lens": np.array(lens["txt"][:12]), "txt_m_lens": np.array(lens["txt"][12:24])}  # (both calls of the student blocks)
+    assert n_lens == {"vit": 12, "txt": 24, "vit_m": 12}, n_lens
+    # the queues after the step: the B columns written at the rounded-down pointer (the others must equal the initial queue)
+    p0 = rec["init_ptr"] // B * B
+    for k in ("image_queue", "text_queue"):
+        after = getattr(model, k).numpy()
+        rest = np.ones(queue_size, dtype=bool)
+        rest[p0:p0 + B] = False
+        assert np.array_equal(after[:, rest], init[k].numpy()[:, rest])
+        rec[f"enq_{k}"] = after[:, p0:p0 + B].copy()
+    rec["enq_at"] = p0
+    n = 0
+    for k, v in model.named_parameters():
+        if v.grad is None:
+            continue
+        flat = v.grad.detach().reshape(-1)
+        ix = grad_sample_index(flat.numel(), nsample)
+        rec[f"g_{k}_sample"] = flat[torch.from_numpy(ix)].numpy()
+        rec[f"g_{k}_norm"] = np.float64(flat.double().norm().item())
+        n += 1
+    for k, v in model.named_parameters():
+        if id(v) in momentum:
+            flat = v.detach().reshape(-1)
+            rec[f"m_{k}"] = flat[torch.from_numpy(grad_sample_index(flat.numel(), 16, stride=104729))].numpy()
+    torch.optim.SGD([p_ for p_ in model.parameters() if p_.grad is not None], lr=lr).step()
+    with torch.no_grad():
+        losses2 = model(images, ["caption"] * B, alpha, idx_t, temperature=temperature)
+    for h in hooks:
+        h.remove()
+    tap.restore()
+    rec["losses2"] = np.array([float(x) for x in losses2], dtype=np.float64)
+    np.savez_compressed(os.path.join(GOLD, name + ".npz"), **rec)
+    print(f"[{name}] T={temperature} eot={rec['eot_pos'].tolist()} lens={ {t: v.tolist() for t, v in rec.items() if t.endswith('_lens')} } "
+          f"losses={rec['losses'].round(5).tolist()} losses2={rec['losses2'].round(5).tolist()} {n} gradients")
+
+
 L14 = dict(patch=14, vision_width=1024, vision_layers=24, embed_dim=768, text_width=768)
 
 CASES = {
@@ -1369,6 +1481,10 @@ CASES = {
     # the retrieval training step (BLIP_Retrieval.forward, evaluate=False): duplicate ids, ids shared with the queue, T = 20 and 0
     "trainstep_retr_b3_T20": lambda: retr_train_case("trainstep_retr_b3_T20", 3, 96, 20, 20.0, [5, 7, 5], 0.4, 12),
     "trainstep_retr_b4_T0": lambda: retr_train_case("trainstep_retr_b4_T0", 4, 96, 16, 0.0, [3, 8, 9, 4], 0.4, 12, seed=1),
+    # the CLIP training step (CLIP.forward, evaluate=False): a duplicate id in the batch, an id shared with the queue, captions of
+    # 5 .. 60 words with one EOT near position 40
+    "trainstep_clip_b4_T0": lambda: clip_train_case("trainstep_clip_b4_T0", 4, 0.0, [3, 8, 3, 4], [5, 39, 60, 14], seed=1),
+    "trainstep_clip_b3_T4": lambda: clip_train_case("trainstep_clip_b3_T4", 3, 4.0, [5, 7, 5], [7, 39, 22]),
     "modelgrad_nlvr_b2": lambda: nlvr_model_grad_case("modelgrad_nlvr_b2", 2, 96, 35, 30.0, pad_tail=0, nsample=64),
     "nlvrgrad_b3_l3": lambda: nlvr_layer_grad_case("nlvrgrad_b3_l3", 3, 35, 30.0, layer=3, pad_tail=3),
     "nlvrgrad_b3_l7": lambda: nlvr_layer_grad_case("nlvrgrad_b3_l7", 3, 35, 30.0, layer=7, pad_tail=3),
