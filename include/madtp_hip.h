@@ -727,7 +727,8 @@ int madtp_attention_bwd(const float* q, const float* k, const float* v, int ld, 
  *   loss[b] = -sum_j t_j log softmax(s)_j,  dq = d mean_b(loss) / dq  [B,D],  dtemp = d mean_b(loss) / d temp  [1].
  * The gradient is formed here, before the caller overwrites the queue.  Fixed-order reductions, no atomics: bit-identical
  * across identical calls.  ws: device workspace of madtp_itc_workspace(B, D, Q) bytes.
- * D % 64 == 0, D <= 512, 1 <= B <= 256, Q >= 0 (queue / idx_queue may be NULL when Q == 0). */
+ * D % 64 == 0, D <= 1024, 1 <= B <= 256, Q >= 0 (queue / idx_queue may be NULL when Q == 0).  D <= 512 runs scalar-FMA tiles,
+ * 512 < D <= 1024 (CLIP ViT-L/14: 768) the same two passes on v_mfma_f32_16x16x4_f32 - exact f32 products either way. */
 size_t madtp_itc_workspace(int B, int D, int Q);
 int madtp_itc_loss(const float* q, const float* q_m, const float* keys_batch, const float* queue, const int64_t* idx,
                    const int64_t* idx_queue, const float* temp, float alpha, float* loss, float* dq, float* dtemp, void* ws,

@@ -406,7 +406,7 @@ class CLIP(nn.Module):
         temp = exp(-logit_scale) formed on the device, BEFORE the queues advance (the gradient is formed there); the STUDENT
         features are what the reference enqueues (:572).  temperature = 0: loss_fdt and loss_fdt_m are loss_ita itself.
         With a process group the features and ids are gathered for the queue (blip_retrieval._all_gather).
-        Needs runtime.precision('fp32') or 'f16x3' (with runtime.training_f16x3()); embed_dim <= 512 (madtp_itc_loss)."""
+        Needs runtime.precision('fp32') or 'f16x3' (with runtime.training_f16x3()); embed_dim % 64 == 0 and <= 1024 (madtp_itc_loss)."""
         if self.evaluate:
             raise NotImplementedError("CLIP(evaluate=True) is the evaluation model (encode_image / encode_text): build it with "
                                       "evaluate=False to train")

@@ -220,6 +220,207 @@ __device__ __forceinline__ void itc_stat_merge(ItcStat& x, const ItcStat& y) {
     x.NP += y.NP;
 }
 
+// ================================ ITC, wide features (512 < D <= 1024): the same two passes on the exact-f32 MFMA =============
+// v_mfma_f32_16x16x4_f32 forms every product: bitwise an fmaf chain, at the vector FP32 rate, with one LDS read per operand per
+// 16 x 16 x 4 block instead of one per FMA.  A workgroup owns 16 query rows (the CLIP driver's batch) and walks 64-column key
+// tiles; wave w owns columns 16 w .. 16 w + 15 of the tile and its s and s_m accumulators share every key fragment.  Tiles
+// never straddle the in-batch keys and the queue: the first ceil(B / 64) tiles are rows of kb, the rest columns of the queue
+// from its column 0, so a queue tile chunk is 64 rows of 256 contiguous bytes and is staged with 16-byte loads.
+// Lane l = (c, g) = (l & 15, l >> 4).  Operands: A[row c][k = g], B[k = g][col c]; result register i: [row 4 g + i][col c].
+// Pass 1 / the scores of pass 2: the four k of step (j, e) are the features 16 j + 4 g + e of the chunk, so the lane's q values
+//   of four steps are one 16-byte LDS read and, with the 68-float rows of Ks, the four key rows of a step start 16 banks apart.
+// Pass 2: dq[16, D] += W K^T with W = (p - t) / temp through LDS; the k of a step are the tile columns 16 j + 4 g + e (16-byte
+//   reads of both operands) and wave w owns features 16 w .. 16 w + 15 of every chunk: NDC accumulator tiles per lane.
+constexpr int ITCW_RT = 16;
+constexpr int ITCW_LD = 68;  // floats per LDS row: 16-byte aligned rows, 68 r mod 64 = 4 r
+constexpr int ITCW_MAX_SPLITS = 1024;  // one key tile per workgroup at Q = 57 600 (901 tiles): ~3.5 workgroups per CU per row tile
+
+__device__ __forceinline__ void itcw_stage_keys(const ItcArgs& a, float (*Ks)[ITCW_LD], int tile, int nbt, int dc, bool vec) {
+    if (tile < nbt) {  // in-batch keys: rows of kb
+        for (int e = threadIdx.x; e < ITC_CT * ITC_DC; e += ITC_THREADS) {
+            const int cc = e / ITC_DC, dd = e % ITC_DC, col = tile * ITC_CT + cc;
+            Ks[dd][cc] = col < a.B ? a.kb[(size_t)col * a.D + dc * ITC_DC + dd] : 0.f;
+        }
+        return;
+    }
+    const int q0 = (tile - nbt) * ITC_CT;
+    if (vec) {  // Q % 4 == 0 and a 16-byte aligned queue: whole float4 are inside or outside
+        for (int e = threadIdx.x; e < ITC_DC * (ITC_CT / 4); e += ITC_THREADS) {
+            const int dd = e / (ITC_CT / 4), c4 = (e % (ITC_CT / 4)) * 4, qi = q0 + c4;
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
+            if (qi < a.Q) v = *(const f32x4*)(a.queue + (size_t)(dc * ITC_DC + dd) * a.Q + qi);
+            *(f32x4*)&Ks[dd][c4] = v;
+        }
+    } else {
+        for (int e = threadIdx.x; e < ITC_DC * ITC_CT; e += ITC_THREADS) {
+            const int dd = e / ITC_CT, cc = e % ITC_CT, qi = q0 + cc;
+            Ks[dd][cc] = qi < a.Q ? a.queue[(size_t)(dc * ITC_DC + dd) * a.Q + qi] : 0.f;
+        }
+    }
+}
+
+__device__ __forceinline__ void itcw_stage_rows(const ItcArgs& a, float (*Qs)[ITCW_LD], float (*Qms)[ITCW_LD], int r0, int dc) {
+    for (int e = threadIdx.x; e < ITCW_RT * ITC_DC; e += ITC_THREADS) {
+        const int r = e / ITC_DC, dd = e % ITC_DC, row = r0 + r;
+        const bool ok = row < a.B;
+        Qs[r][dd] = ok ? a.q[(size_t)row * a.D + dc * ITC_DC + dd] : 0.f;
+        Qms[r][dd] = ok ? a.qm[(size_t)row * a.D + dc * ITC_DC + dd] : 0.f;
+    }
+}
+
+__device__ __forceinline__ ItcStat itc_stat_shfl_xor(const ItcStat& x, int m) {
+    return {__shfl_xor(x.M, m), __shfl_xor(x.L, m), __shfl_xor(x.MM, m), __shfl_xor(x.LM, m),
+            __shfl_xor(x.AM, m), __shfl_xor(x.P, m), __shfl_xor(x.NP, m)};
+}
+
+template <int NDC, bool PASS2>
+__global__ __launch_bounds__(ITC_THREADS) void itc_wide_kernel(ItcArgs a) {
+    __shared__ __attribute__((aligned(16))) float Qs[ITCW_RT][ITCW_LD];
+    __shared__ __attribute__((aligned(16))) float Qms[ITCW_RT][ITCW_LD];
+    __shared__ __attribute__((aligned(16))) float Ks[ITC_DC][ITCW_LD];
+    __shared__ __attribute__((aligned(16))) float Ws[PASS2 ? ITCW_RT : 1][ITCW_LD];
+    __shared__ float red[ITCW_RT][4][PASS2 ? 1 : 7];
+    const int t = threadIdx.x, w = t >> 6, c = t & 15, g = (t >> 4) & 3;
+    const int r0 = blockIdx.x * ITCW_RT, split = blockIdx.y;
+    const float temp = *a.temp;
+    const int nbt = (a.B + ITC_CT - 1) / ITC_CT, ntiles = nbt + (a.Q + ITC_CT - 1) / ITC_CT;
+    const int tile0 = split * a.tiles_per_split, tile1 = min(ntiles, tile0 + a.tiles_per_split);
+    const bool vec = (a.Q & 3) == 0 && (((uintptr_t)a.queue) & 15u) == 0;
+    // result register i of this lane is row 4 g + i
+    int64_t my_id[4];
+    float rinfo[4][3];
+    for (int i = 0; i < 4; ++i) {
+        const int row = r0 + 4 * g + i;
+        my_id[i] = row < a.B ? a.idx[row] : INT64_MIN;
+        for (int k = 0; k < 3; ++k) rinfo[i][k] = (PASS2 && row < a.B) ? a.rowinfo[row * 4 + k] : 0.f;
+    }
+    ItcStat st[4];
+    for (int i = 0; i < 4; ++i) st[i] = itc_stat_empty();
+    f32x4 dacc[NDC];
+    for (int dc = 0; dc < NDC; ++dc) dacc[dc] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float wsum[4] = {0.f, 0.f, 0.f, 0.f};
+
+    for (int tile = tile0; tile < tile1; ++tile) {
+        f32x4 s = {0.f, 0.f, 0.f, 0.f}, sm = {0.f, 0.f, 0.f, 0.f};
+        for (int dc = 0; dc < NDC; ++dc) {
+            itcw_stage_rows(a, Qs, Qms, r0, dc);
+            itcw_stage_keys(a, Ks, tile, nbt, dc, vec);
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f32x4 qa = *(const f32x4*)&Qs[c][16 * j + 4 * g], qma = *(const f32x4*)&Qms[c][16 * j + 4 * g];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float kv = Ks[16 * j + 4 * g + e][16 * w + c];
+                    s = __builtin_amdgcn_mfma_f32_16x16x4f32(qa[e], kv, s, 0, 0, 0);
+                    sm = __builtin_amdgcn_mfma_f32_16x16x4f32(qma[e], kv, sm, 0, 0, 0);
+                }
+            }
+            __syncthreads();
+        }
+        // this lane's column of the tile, its validity and id
+        const int cc = 16 * w + c;
+        bool colok;
+        int64_t cid = 0;
+        if (tile < nbt) {
+            const int col = tile * ITC_CT + cc;
+            colok = col < a.B;
+            if (colok) cid = a.idx[col];
+        } else {
+            const int qi = (tile - nbt) * ITC_CT + cc;
+            colok = qi < a.Q;
+            if (colok) cid = a.idxq[qi];
+        }
+        for (int i = 0; i < 4; ++i) {
+            const bool ok = colok && r0 + 4 * g + i < a.B;
+            const float sv = s[i] / temp, smv = sm[i] / temp;
+            const bool pos = ok && cid == my_id[i];
+            if constexpr (!PASS2) {
+                if (ok) {
+                    ItcStat& x = st[i];
+                    online_add(x.M, x.L, sv);
+                    const float mn = fmaxf(x.MM, smv), sc = expf(x.MM - mn), ex = expf(smv - mn);
+                    x.LM = x.LM * sc + ex;
+                    x.AM = fmaf(ex, sv, x.AM * sc);
+                    x.MM = mn;
+                    if (pos) { x.P += sv; x.NP += 1.f; }
+                }
+            } else {
+                float wv = 0.f;
+                if (ok) {
+                    const float tgt = a.alpha * expf(smv - rinfo[i][1]) + (pos ? rinfo[i][2] : 0.f);
+                    wv = expf(sv - rinfo[i][0]) - tgt;
+                    wsum[i] = fmaf(wv, sv, wsum[i]);
+                }
+                Ws[4 * g + i][cc] = wv / temp;
+            }
+        }
+        if constexpr (PASS2) {
+            __syncthreads();
+            f32x4 wa[4];
+            for (int j = 0; j < 4; ++j) wa[j] = *(const f32x4*)&Ws[c][16 * j + 4 * g];
+#pragma unroll
+            for (int dc = 0; dc < NDC; ++dc) {
+                itcw_stage_keys(a, Ks, tile, nbt, dc, vec);
+                __syncthreads();
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const f32x4 kv = *(const f32x4*)&Ks[16 * w + c][16 * j + 4 * g];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dacc[dc] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[j][e], kv[e], dacc[dc], 0, 0, 0);
+                }
+                __syncthreads();
+            }
+        }
+    }
+    // the 16 column lanes of a wave by a fixed xor tree, then the four waves in order
+    for (int i = 0; i < 4; ++i) {
+        for (int m = 1; m < 16; m <<= 1) {
+            if constexpr (!PASS2) {
+                const ItcStat y = itc_stat_shfl_xor(st[i], m);
+                itc_stat_merge(st[i], y);
+            } else {
+                wsum[i] += __shfl_xor(wsum[i], m);
+            }
+        }
+        if (c == 0) {
+            float* r = red[4 * g + i][w];
+            if constexpr (!PASS2) {
+                const ItcStat& x = st[i];
+                r[0] = x.M; r[1] = x.L; r[2] = x.MM; r[3] = x.LM; r[4] = x.AM; r[5] = x.P; r[6] = x.NP;
+            } else {
+                r[0] = wsum[i];
+            }
+        }
+    }
+    __syncthreads();
+    if (t < ITCW_RT && r0 + t < a.B) {
+        const int row = r0 + t;
+        if constexpr (!PASS2) {
+            ItcStat x = itc_stat_empty();
+            for (int k = 0; k < 4; ++k) {
+                const float* r = red[t][k];
+                const ItcStat y = {r[0], r[1], r[2], r[3], r[4], r[5], r[6]};
+                itc_stat_merge(x, y);
+            }
+            float* o = a.stats + ((size_t)split * a.B + row) * ITC_NSTAT;
+            o[0] = x.M; o[1] = x.L; o[2] = x.MM; o[3] = x.LM; o[4] = x.AM; o[5] = x.P; o[6] = x.NP; o[7] = 0.f;
+        } else {
+            float sum = 0.f;
+            for (int k = 0; k < 4; ++k) sum += red[t][k][0];
+            a.dtpart[(size_t)split * a.B + row] = -sum / temp;
+        }
+    }
+    if constexpr (PASS2) {
+        for (int i = 0; i < 4; ++i) {
+            const int row = r0 + 4 * g + i;
+            if (row >= a.B) continue;
+            float* o = a.dqpart + ((size_t)split * a.B + row) * a.D + 16 * w + c;
+            for (int dc = 0; dc < NDC; ++dc) o[dc * ITC_DC] = dacc[dc][i];
+        }
+    }
+}
+
 // one wave per row: lane l merges splits l, l + 64, ... in order, then a fixed pairwise tree over the lanes
 // -> loss, logZ, logZm, (1 - alpha) / n_pos
 constexpr int ITC_C1_THREADS = 64;
@@ -283,7 +484,15 @@ __global__ __launch_bounds__(ITC_C2_THREADS) void itc_combine2_kernel(ItcArgs a)
     if (t == 0) *a.dtemp = part[0] * invB;
 }
 
-void itc_geometry(int B, int Q, int& rowtiles, int& splits, int& tiles_per_split) {
+void itc_geometry(int B, int D, int Q, int& rowtiles, int& splits, int& tiles_per_split) {
+    if (D > 512) {  // the wide kernel: 16-row tiles, key tiles that do not straddle the in-batch keys and the queue
+        const int ntiles = (B + ITC_CT - 1) / ITC_CT + (Q + ITC_CT - 1) / ITC_CT;
+        rowtiles = (B + ITCW_RT - 1) / ITCW_RT;
+        const int want = std::max(1, std::min(ITCW_MAX_SPLITS, 2048 / rowtiles));
+        tiles_per_split = (ntiles + want - 1) / want;
+        splits = (ntiles + tiles_per_split - 1) / tiles_per_split;
+        return;
+    }
     const int N = B + Q, ntiles = (N + ITC_CT - 1) / ITC_CT;
     rowtiles = (B + ITC_RT - 1) / ITC_RT;
     int want = std::max(1, std::min(ITC_MAX_SPLITS, 2048 / rowtiles));
@@ -296,6 +505,14 @@ void itc_launch(const ItcArgs& a, int rowtiles, hipStream_t s) {
     hipLaunchKernelGGL((itc_pass_kernel<NDC, false>), dim3(rowtiles, a.splits), dim3(ITC_THREADS), 0, s, a);
     hipLaunchKernelGGL(itc_combine1_kernel, dim3(a.B), dim3(ITC_C1_THREADS), 0, s, a);
     hipLaunchKernelGGL((itc_pass_kernel<NDC, true>), dim3(rowtiles, a.splits), dim3(ITC_THREADS), 0, s, a);
+    hipLaunchKernelGGL(itc_combine2_kernel, dim3(a.B + 1, a.D / ITC_DC), dim3(ITC_C2_THREADS), 0, s, a);
+}
+
+template <int NDC>
+void itc_wide_launch(const ItcArgs& a, int rowtiles, hipStream_t s) {
+    hipLaunchKernelGGL((itc_wide_kernel<NDC, false>), dim3(rowtiles, a.splits), dim3(ITC_THREADS), 0, s, a);
+    hipLaunchKernelGGL(itc_combine1_kernel, dim3(a.B), dim3(ITC_C1_THREADS), 0, s, a);
+    hipLaunchKernelGGL((itc_wide_kernel<NDC, true>), dim3(rowtiles, a.splits), dim3(ITC_THREADS), 0, s, a);
     hipLaunchKernelGGL(itc_combine2_kernel, dim3(a.B + 1, a.D / ITC_DC), dim3(ITC_C2_THREADS), 0, s, a);
 }
 
@@ -409,7 +626,7 @@ __global__ __launch_bounds__(NEG_THREADS) void itm_neg_kernel(const float* img, 
 extern "C" size_t madtp_itc_workspace(int B, int D, int Q) {
     if (B <= 0 || D <= 0 || Q < 0) return 0;
     int rowtiles, splits, tps;
-    itc_geometry(B, Q, rowtiles, splits, tps);
+    itc_geometry(B, D, Q, rowtiles, splits, tps);
     return sizeof(float) * ((size_t)splits * B * ITC_NSTAT + (size_t)B * 4 + (size_t)splits * B * D + (size_t)splits * B);
 }
 
@@ -419,13 +636,13 @@ extern "C" int madtp_itc_loss(const float* q, const float* q_m, const float* key
     if (!q || !q_m || !keys_batch || !idx || !temp || !loss || !dq || !dtemp || !ws || B <= 0 || D <= 0 || Q < 0)
         return MADTP_E_BADARG;
     if (Q > 0 && (!queue || !idx_queue)) return MADTP_E_BADARG;
-    if (D % ITC_DC != 0 || D > 512 || B > 256) return MADTP_E_SHAPE;
+    if (D % ITC_DC != 0 || D > 1024 || B > 256) return MADTP_E_SHAPE;
     if (ws_bytes < madtp_itc_workspace(B, D, Q)) return MADTP_E_BADARG;
     ItcArgs a;
     a.q = q; a.qm = q_m; a.kb = keys_batch; a.queue = queue; a.idx = idx; a.idxq = idx_queue; a.temp = temp; a.alpha = alpha;
     a.B = B; a.D = D; a.Q = Q; a.N = B + Q;
     int rowtiles;
-    itc_geometry(B, Q, rowtiles, a.splits, a.tiles_per_split);
+    itc_geometry(B, D, Q, rowtiles, a.splits, a.tiles_per_split);
     float* w = (float*)ws;
     a.stats = w; w += (size_t)a.splits * B * ITC_NSTAT;
     a.rowinfo = w; w += (size_t)B * 4;
@@ -441,7 +658,15 @@ extern "C" int madtp_itc_loss(const float* q, const float* q_m, const float* key
         case 5: itc_launch<5>(a, rowtiles, s); break;
         case 6: itc_launch<6>(a, rowtiles, s); break;
         case 7: itc_launch<7>(a, rowtiles, s); break;
-        default: itc_launch<8>(a, rowtiles, s); break;
+        case 8: itc_launch<8>(a, rowtiles, s); break;
+        case 9: itc_wide_launch<9>(a, rowtiles, s); break;
+        case 10: itc_wide_launch<10>(a, rowtiles, s); break;
+        case 11: itc_wide_launch<11>(a, rowtiles, s); break;
+        case 12: itc_wide_launch<12>(a, rowtiles, s); break;
+        case 13: itc_wide_launch<13>(a, rowtiles, s); break;
+        case 14: itc_wide_launch<14>(a, rowtiles, s); break;
+        case 15: itc_wide_launch<15>(a, rowtiles, s); break;
+        default: itc_wide_launch<16>(a, rowtiles, s); break;
     }
     MADTP_LAUNCH_CHECK();
     return 0;

@@ -1452,7 +1452,8 @@ def _gpu_i64(t, name):
 
 def itc_loss(q, q_m, keys_batch, queue, idx, idx_queue, temp, alpha):
     """One direction of the contrastive loss (madtp_itc_loss): q, q_m, keys_batch f32 [B,D]; queue f32 [D,Q]; idx int64 [B];
-    idx_queue int64 [Q]; temp f32 [] or [1] on the device -> (loss [B], dq [B,D] = d mean(loss)/dq, dtemp [1])."""
+    idx_queue int64 [Q]; temp f32 [] or [1] on the device -> (loss [B], dq [B,D] = d mean(loss)/dq, dtemp [1]).
+    D % 64 == 0, D <= 1024, B <= 256; anything else raises."""
     for t, n in ((q, "q"), (q_m, "q_m"), (keys_batch, "keys_batch"), (queue, "queue")):
         _gpu_f32(t, f"itc_loss: {n}", 2)
     _gpu_i64(idx, "itc_loss: idx")

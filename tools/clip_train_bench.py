@@ -2,7 +2,7 @@
 """CLIP's training step and its two embedding kernels (csrc/clip.hip) at the shape of configs/retrieval_coco_clip.yaml's loop
 on the ViT-B/16 checkpoint geometry: B = 16, 224^2, text 77 x 512, vocabulary 49408, Q = 57 600, one GPU.
 
-    python tools/clip_train_bench.py [--iters N] [--rounds R] [--out profiles/clip_train_step.json] [--no-step]
+    python tools/clip_train_bench.py [--iters N] [--rounds R] [--out profiles/clip_train_step.json] [--no-step] [--arch B16|L14]
 
   embed_grad: madtp_embedding_grad (rank + ordered segmented sum, every row of the [49408, 512] gradient written once)  vs  the
               composition it replaces, torch.zeros_like(table).index_add_(0, ids, dx) (a 101 MB memset and atomic adds);
@@ -11,7 +11,10 @@ on the ViT-B/16 checkpoint geometry: B = 16, 224^2, text 77 x 512, vocabulary 49
 The two sides of each pair alternate inside every round (shared machine: a drift hits both); each side's figure is the median over
 the rounds of its per-round median of device-event intervals, reported with the min and max of those per-round medians.  Captions
 are CLIP-shaped: SOT, 6 .. 40 words, EOT, zero padding (synth.synth_clip_tokens), so about 49 of 77 positions share id 0.
-Bytes: the algorithm's own (read ids and dx once, write the gradient once), over the measured time, against 8 TB/s."""
+Bytes: the algorithm's own (read ids and dx once, write the gradient once), over the measured time, against 8 TB/s.
+--arch L14: the geometry the reference's two CLIP configs train (clip_large_retrieval_*.pth, ViT-L/14@336): vision width 1024 /
+24 layers / patch 14 at 336^2, text 77 x 768 / 12 layers, embed_dim 768; B = 16, Q = 57 600.  Default out:
+profiles/clip_l14_train_step.json."""
 import argparse
 import json
 import os
@@ -26,6 +29,9 @@ from madtp_amd import hip, runtime, specs, synth  # noqa: E402
 from madtp_amd.clip_model import CLIP  # noqa: E402
 
 HBM = 8.0e12
+# text width (= table width D), image size, patch, vision width, vision layers, embed_dim
+ARCHS = {"B16": dict(D=512, size=224, patch=16, vision_width=768, vision_layers=12, embed_dim=512),
+         "L14": dict(D=768, size=336, patch=14, vision_width=1024, vision_layers=24, embed_dim=768)}
 
 
 def _median_us(fn, iters):
@@ -57,15 +63,20 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "clip_train_step.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--arch", choices=sorted(ARCHS), default="B16")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "clip_train_step.json" if a.arch == "B16" else "clip_l14_train_step.json")
+    arch = ARCHS[a.arch]
     if not torch.cuda.is_available():
         raise SystemExit("clip_train_bench: needs the GPU (a CPU run measures nothing)")
     hip.load()
     dev = "cuda"
-    B, L, D, V, Q, size = 16, 77, 512, 49408, 57600, 224
-    res = {"B": B, "L": L, "D": D, "V": V, "Q": Q, "image": size, "iters": a.iters, "rounds": a.rounds,
+    B, L, D, V, Q, size = 16, 77, arch["D"], 49408, 57600, arch["size"]
+    res = {"arch": a.arch, "B": B, "L": L, "D": D, "embed_dim": arch["embed_dim"], "V": V, "Q": Q, "image": size, "iters": a.iters,
+           "rounds": a.rounds,
            "device": torch.cuda.get_device_name(0)}
     text = synth.synth_clip_tokens(B, L, 0).to(dev)
     g = torch.Generator(device=dev).manual_seed(0)
@@ -93,8 +104,10 @@ def main():
 
     if not a.no_step:
         with torch.no_grad():
-            model = CLIP(D, size, 12, 768, 16, L, V, 512, 8, 12, False, None, queue_size=Q)
-            model.load_state_dict(specs.synth_weights(specs.clip_shapes(size), 0), strict=False)
+            model = CLIP(arch["embed_dim"], size, arch["vision_layers"], arch["vision_width"], arch["patch"], L, V, D, D // 64, 12,
+                         False, None, queue_size=Q)
+            model.load_state_dict(specs.synth_weights(specs.clip_shapes(size, arch["patch"], arch["vision_width"], arch["vision_layers"],
+                                                                        arch["embed_dim"], D, 12), 0), strict=False)
             model.copy_params()
             model = model.to(dev).eval()
         images = synth.synth_images(B, size, 0, device=dev)

@@ -1330,9 +1330,11 @@ def clip_train_tokens(lens, seed):
     return torch.cat([synth.synth_clip_tokens(1, 77, 100 * seed + b, n, n) for b, n in enumerate(lens)], 0)
 
 
-def clip_train_case(name, B, temperature, idx, cap_lens, alpha=0.4, queue_size=48, seed=0, size=96, nsample=32, lr=0.05):
-    """The reference's OWN CLIP training step (clip/model.py:529-595, CLIP(evaluate=False), model.eval()) at world 1 on the
-    ViT-B/16 geometry at 96^2 (37 tokens) with the 12-layer text tower: student towers, EMA, momentum pass (encode_text_m runs
+def clip_train_case(name, B, temperature, idx, cap_lens, alpha=0.4, queue_size=48, seed=0, size=96, nsample=32, lr=0.05,
+                    patch=16, vision_width=768, vision_layers=12, embed_dim=512, text_width=512, text_layers=12):
+    """The reference's OWN CLIP training step (clip/model.py:529-595, CLIP(evaluate=False), model.eval()) at world 1, by default on
+    the ViT-B/16 geometry at 96^2 (37 tokens) with the 12-layer text tower (the geometry keywords are those of clip_full_case;
+    heads = width // 64 in both towers): student towers, EMA, momentum pass (encode_text_m runs
     the STUDENT transformer, :516), ITC against a small seeded queue, dequeue-and-enqueue of the student features;
     loss = loss_ita + 0.1 loss_fdt + 0.1 loss_fdt_m as compress_retrieval_clip_dtp.py does.  For this recording only the kept
     tokens of every pruning step are put in ascending order (CanonicalTap).  Then torch.optim.SGD(lr) steps on the gradients and a
@@ -1342,9 +1344,10 @@ def clip_train_case(name, B, temperature, idx, cap_lens, alpha=0.4, queue_size=4
     from madtp_amd import specs
     cm.concat_all_gather = lambda t: t  # world 1
     torch.manual_seed(seed)
-    model = cm.CLIP(512, size, 12, 768, 16, 77, 49408, 512, 8, 12, False, None)
+    model = cm.CLIP(embed_dim, size, vision_layers, vision_width, patch, 77, 49408, text_width, text_width // 64, text_layers,
+                    False, None)
     model.eval()
-    sd = specs.synth_weights(specs.clip_shapes(size), seed)
+    sd = specs.synth_weights(specs.clip_shapes(size, patch, vision_width, vision_layers, embed_dim, text_width, text_layers), seed)
     sd["logit_scale"] = torch.tensor(2.6592600369327779)  # log(1 / 0.07), the reference's initial value (:387)
     msg = model.load_state_dict(sd, strict=False)
     assert not msg.unexpected_keys, msg.unexpected_keys
@@ -1354,8 +1357,8 @@ def clip_train_case(name, B, temperature, idx, cap_lens, alpha=0.4, queue_size=4
     iq = torch.full((1, queue_size), -100, dtype=torch.long)
     iq[0, 1] = idx[-1]                     # an id of the batch already in the queue
     iq[0, queue_size // 2] = 11
-    init = {"image_queue": torch.nn.functional.normalize(torch.randn(512, queue_size, generator=g), dim=0),
-            "text_queue": torch.nn.functional.normalize(torch.randn(512, queue_size, generator=g), dim=0),
+    init = {"image_queue": torch.nn.functional.normalize(torch.randn(embed_dim, queue_size, generator=g), dim=0),
+            "text_queue": torch.nn.functional.normalize(torch.randn(embed_dim, queue_size, generator=g), dim=0),
             "idx_queue": iq, "ptr_queue": torch.tensor([B + 1], dtype=torch.long)}  # (an unaligned pointer: rounded down, :609-610)
     for k, v in init.items():
         setattr(model, k, v.clone())
@@ -1390,8 +1393,9 @@ def clip_train_case(name, B, temperature, idx, cap_lens, alpha=0.4, queue_size=4
            "losses": np.array([float(x) for x in losses], dtype=np.float64),
            "idx_queue": model.idx_queue.numpy().copy(), "ptr": int(model.ptr_queue[0]),
            "vit_lens": np.array(lens["vit"]), "vit_m_lens": np.array(lens["vit_m"]),
-           "txt_lens": np.array(lens["txt"][:12]), "txt_m_lens": np.array(lens["txt"][12:24])}  # (both calls of the student blocks)
-    assert n_lens == {"vit": 12, "txt": 24, "vit_m": 12}, n_lens
+           "txt_lens": np.array(lens["txt"][:text_layers]),
+           "txt_m_lens": np.array(lens["txt"][text_layers:2 * text_layers])}  # (both calls of the student blocks)
+    assert n_lens == {"vit": vision_layers, "txt": 2 * text_layers, "vit_m": vision_layers}, n_lens
     # the queues after the step: the B columns written at the rounded-down pointer (the others must equal the initial queue)
     p0 = rec["init_ptr"] // B * B
     for k in ("image_queue", "text_queue"):
@@ -1485,6 +1489,11 @@ CASES = {
     # 5 .. 60 words with one EOT near position 40
     "trainstep_clip_b4_T0": lambda: clip_train_case("trainstep_clip_b4_T0", 4, 0.0, [3, 8, 3, 4], [5, 39, 60, 14], seed=1),
     "trainstep_clip_b3_T4": lambda: clip_train_case("trainstep_clip_b3_T4", 3, 4.0, [5, 7, 5], [7, 39, 22]),
+    # the same step at the ViT-L/14 widths (vision 1024 / 16 heads, text 768 / 12 heads, embed_dim 768) with 4 layers per tower
+    # at 112^2 (65 tokens): every block applies the same pruning rule, and clipl14vitgrad_b2 covers the 24-layer depth
+    "trainstep_clipl14_b3_T4": lambda: clip_train_case("trainstep_clipl14_b3_T4", 3, 4.0, [5, 7, 5], [7, 39, 22], queue_size=24,
+                                                       size=112, patch=14, vision_width=1024, vision_layers=4, embed_dim=768,
+                                                       text_width=768, text_layers=4),
     "modelgrad_nlvr_b2": lambda: nlvr_model_grad_case("modelgrad_nlvr_b2", 2, 96, 35, 30.0, pad_tail=0, nsample=64),
     "nlvrgrad_b3_l3": lambda: nlvr_layer_grad_case("nlvrgrad_b3_l3", 3, 35, 30.0, layer=3, pad_tail=3),
     "nlvrgrad_b3_l7": lambda: nlvr_layer_grad_case("nlvrgrad_b3_l7", 3, 35, 30.0, layer=7, pad_tail=3),

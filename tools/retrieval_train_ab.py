@@ -2,17 +2,21 @@
 """A/B of the retrieval training step's new kernels (csrc/retrieval.hip) against the eager torch composition they replace, at
 the config shape (B = 32, D = 256, Q = 57 600, ViT-B at 384^2), on one GPU, plus the time of a whole training step.
 
-    python tools/retrieval_train_ab.py [--iters N] [--out FILE.json] [--no-step]
+    python tools/retrieval_train_ab.py [--iters N] [--out FILE.json] [--no-step] [--dim D]
 
   itc: both directions of madtp_itc_loss (forward + gradient)  vs  cat(feat.T, queue.clone()), the four [B, B+Q] similarity
        matrices, softmaxes, log_softmax loss and its autograd backward (blip_retrieval.py:116-150);
   ema: madtp_ema_update over every momentum pair (ema_hip_us: EmaTable.update with its per-step pointer check; ema_kernel_us:
        the launch alone)  vs  the per-tensor `p_m.data = p_m.data * m + p.data * (1 - m)` loop (:296-300);
   neg: madtp_itm_negatives  vs  the softmax / masked_fill / 2 B torch.multinomial(...).item() loop (:240-258).
-Times are medians of CUDA-event intervals after warm-up.  HBM fraction: bytes moved / time / 8 TB/s (MI355X peak)."""
+Times are medians of CUDA-event intervals after warm-up.  HBM fraction: bytes moved / time / 8 TB/s (MI355X peak).
+--dim D (default 256, BLIP's embed_dim): any other D runs the itc leg alone, at (B 16, Q 57 600) and (B 32, Q 57 600) - CLIP
+ViT-L/14 trains at D = 768, B = 16 - with the two sides alternating inside every round; each figure is the median over the rounds
+of its per-round median, with the min and max of those.  The other legs are BLIP's and stay at D = 256."""
 import argparse
 import json
 import os
+import statistics
 import sys
 
 import torch
@@ -42,16 +46,21 @@ def timed(fn, iters, warm=3):
     return ts[len(ts) // 2]
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--out", default="")
-    ap.add_argument("--no-step", action="store_true")
-    a = ap.parse_args()
-    hip.load()
-    dev = "cuda"
-    B, D, Q = 32, 256, 57600
-    res = {"B": B, "D": D, "Q": Q}
+def ab(fns, iters, rounds=5, warm=5):
+    """{name: fn} -> {name: {"us": median of the per-round medians, "min_us", "max_us"}}; the sides alternate within a round"""
+    for fn in fns.values():
+        for _ in range(warm):
+            fn()
+    torch.cuda.synchronize()
+    per = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            per[k].append(timed(fn, iters, warm=0))
+    return {k: {"us": statistics.median(v), "min_us": min(v), "max_us": max(v)} for k, v in per.items()}
+
+
+def itc_sides(B, D, Q, dev):
+    """-> (itc_hip, itc_torch, (img, txt, idx, temp)): both directions of the loss with its gradient, on seeded unit-norm features"""
     g = torch.Generator(device=dev).manual_seed(0)
     f = lambda n: F.normalize(torch.randn(n, D, device=dev, generator=g), dim=-1)  # noqa: E731
     img, txt, img_m, txt_m = f(B), f(B), f(B), f(B)
@@ -79,6 +88,43 @@ def main():
         li = -torch.sum(F.log_softmax(img_p @ ta / tp, 1) * ti, 1).mean()
         lt = -torch.sum(F.log_softmax(txt_p @ ia / tp, 1) * tt, 1).mean()
         ((li + lt) / 2).backward()
+
+    return itc_hip, itc_torch, (img, txt, idx, temp)
+
+
+def itc_only(a, dev):
+    Q = 57600
+    res = {"D": a.dim, "Q": Q, "iters": a.iters, "rounds": 5, "device": torch.cuda.get_device_name(0), "itc": []}
+    for B in (16, 32):
+        itc_hip, itc_torch, _ = itc_sides(B, a.dim, Q, dev)
+        r = ab({"hip": itc_hip, "torch": itc_torch}, a.iters)
+        res["itc"].append({"B": B, "hip": r["hip"], "torch": r["torch"], "bank_bytes": 4 * a.dim * Q * 4,
+                           "hbm_fraction": 4 * a.dim * Q * 4 / (r["hip"]["us"] * 1e-6) / HBM})
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--out", default="")
+    ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--dim", type=int, default=256)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("retrieval_train_ab: needs the GPU (a CPU run measures nothing)")
+    hip.load()
+    dev = "cuda"
+    if a.dim != 256:
+        res = itc_only(a, dev)
+        print(json.dumps(res))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        return
+    B, D, Q = 32, 256, 57600
+    res = {"B": B, "D": D, "Q": Q}
+    itc_hip, itc_torch, (img, txt, idx, temp) = itc_sides(B, D, Q, dev)
 
     res["itc_hip_us"] = timed(itc_hip, a.iters)
     res["itc_torch_us"] = timed(itc_torch, a.iters)
