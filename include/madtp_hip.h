@@ -767,6 +767,28 @@ size_t madtp_embedding_grad_workspace(int n);
 int madtp_embedding_grad(const int64_t* ids, const float* dx, float* dtable, void* ws, size_t ws_bytes, int n, int D, int V,
                          void* stream);
 
+/* ---- Retrieval evaluation: the drivers' itm_eval without the score matrix, its host copies and the argsort loop (csrc/eval.hip)
+ * Targets are CSR: tgt_ptr int32 [nq+1] (tgt_ptr[nq] = n_targets), tgt_idx int32 [n_targets] key columns.  With s_j the score
+ * of query row r against key j and t one of the row's targets
+ *   rank_tgt = #{j != t : s_j > s_t} + #{j > t : s_j == s_t}
+ * - the position of t in numpy's argsort(s, kind="stable")[::-1]; the target's own column is excluded by index.  NaN scores
+ * compare false.  rank_row[r] = the minimum over the row's targets, nk for a row without one.  A target outside [0, nk) is
+ * never dereferenced: its rank_tgt is nk (score_tgt NaN) and it does not enter the minimum.  At most 16 targets per row: the
+ * kernels ignore the rest, and treat a row whose pointers run backwards or leave [0, tgt_ptr[nq]] as empty.
+ * madtp_rank_embeds: s_j = <q_r, keys_j>, q f32 [nq, ldq], keys f32 [nk, ldk], with exact f32 products on
+ *   v_mfma_f32_16x16x4_f32; score_tgt f32 [n_targets] is bit for bit the value the counting pass compares (and equal for byte
+ *   copies of a key row).  Integer counts, fixed-order sums, no atomics: identical calls give identical bits.
+ *   ws: device workspace of madtp_rank_workspace(nq, nk, D, n_targets) bytes (a row whose targets do not fit the workspace
+ *   the caller gave is treated as empty).  D % 64 == 0, 64 <= D <= 1024, nq, nk >= 1, ldq, ldk >= D and multiples of 4,
+ *   q and keys 16-byte aligned.
+ * madtp_rank_scores: the same rule on a dense row-major f32 matrix scores [nq, ld >= nk] (BLIP's re-ranked score matrices). */
+size_t madtp_rank_workspace(int nq, int nk, int D, int n_targets);
+int madtp_rank_embeds(const float* q, int ldq, const float* keys, int ldk, int nq, int nk, int D, const int32_t* tgt_ptr,
+                      const int32_t* tgt_idx, int32_t* rank_row, int32_t* rank_tgt, float* score_tgt, void* ws, size_t ws_bytes,
+                      void* stream);
+int madtp_rank_scores(const float* scores, int ld, int nq, int nk, const int32_t* tgt_ptr, const int32_t* tgt_idx,
+                      int32_t* rank_row, int32_t* rank_tgt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,10 @@ _SIGS = {
     "madtp_clip_embed": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p]),
     "madtp_embedding_grad_workspace": (c_size_t, [c_int]),
     "madtp_embedding_grad": (c_int, [c_void_p] * 4 + [c_size_t, c_int, c_int, c_int, c_void_p]),
+    # retrieval evaluation (csrc/eval.hip)
+    "madtp_rank_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "madtp_rank_embeds": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 6 + [c_size_t, c_void_p]),
+    "madtp_rank_scores": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 5),
     "madtp_token_gather_bwd": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p]),
     "madtp_token_score_bwd": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4
                               + [c_int, c_int, c_int, c_void_p]),
@@ -1569,3 +1573,57 @@ def embedding_grad(ids, dx, V, out=None):
     ws = torch.empty(max(ws_bytes, 8) // 8 + 1, dtype=torch.int64, device=dx.device)
     _check(lib.madtp_embedding_grad(_p(ids), _p(dx), _p(out), _p(ws), ws.numel() * 8, n, D, V, _stream()), "madtp_embedding_grad")
     return out
+
+
+# ---- retrieval evaluation (include/madtp_hip.h madtp_rank_embeds / madtp_rank_scores) ------------------------------------------
+def _rank_targets(tgt_ptr, tgt_idx, nq, what):
+    for t, n in ((tgt_ptr, "tgt_ptr"), (tgt_idx, "tgt_idx")):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()):
+            raise RuntimeError(f"{what}: {n} must be a contiguous GPU int32 vector (no CPU fallback)")
+    if tgt_ptr.numel() != nq + 1:
+        raise RuntimeError(f"{what}: tgt_ptr has {tgt_ptr.numel()} entries for {nq} rows")
+
+
+def _rank_rows(t, name):
+    """-> the leading dimension of a GPU f32 row-major 2-D view (the strides of size-1 dimensions carry no meaning)"""
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] > 0 and t.shape[1] > 0
+            and (t.stride(1) == 1 or t.shape[1] == 1)):
+        raise RuntimeError(f"{name} must be a GPU f32 row-major 2-D view (no CPU fallback)")
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def rank_embeds(q, keys, tgt_ptr, tgt_idx):
+    """Ranks of the targets among <q_r, keys_j> (madtp_rank_embeds): q f32 [nq,D], keys f32 [nk,D] (row-major views), CSR targets
+    int32 -> (rank_row int32 [nq], rank_tgt int32 [n_targets], score_tgt f32 [n_targets]).  No [nq,nk] matrix is formed."""
+    ldq, ldk = _rank_rows(q, "rank_embeds: q"), _rank_rows(keys, "rank_embeds: keys")
+    nq, D = q.shape
+    nk = keys.shape[0]
+    if keys.shape[1] != D:
+        raise RuntimeError("rank_embeds: q and keys disagree on the feature dimension")
+    _rank_targets(tgt_ptr, tgt_idx, nq, "rank_embeds")
+    nt = tgt_idx.numel()
+    if nt == 0:  # no ground truth at all: nothing to launch, every row ranks nk
+        return (torch.full((nq,), nk, dtype=torch.int32, device=q.device), torch.empty(0, dtype=torch.int32, device=q.device),
+                torch.empty(0, dtype=torch.float32, device=q.device))
+    lib = load()
+    ws = torch.empty(max(int(lib.madtp_rank_workspace(nq, nk, D, nt)), 4) // 4, dtype=torch.int32, device=q.device)
+    rank_row = torch.empty(nq, dtype=torch.int32, device=q.device)
+    rank_tgt = torch.empty(nt, dtype=torch.int32, device=q.device)
+    score_tgt = torch.empty(nt, dtype=torch.float32, device=q.device)
+    _check(lib.madtp_rank_embeds(_p(q), ldq, _p(keys), ldk, nq, nk, D, _p(tgt_ptr), _p(tgt_idx), _p(rank_row),
+                                 _p(rank_tgt), _p(score_tgt), _p(ws), ws.numel() * 4, _stream()), "madtp_rank_embeds")
+    return rank_row, rank_tgt, score_tgt
+
+
+def rank_scores(scores, tgt_ptr, tgt_idx):
+    """The same ranks on a dense f32 score matrix [nq,nk] (madtp_rank_scores) -> (rank_row, rank_tgt)."""
+    ld = _rank_rows(scores, "rank_scores: scores")
+    nq, nk = scores.shape
+    _rank_targets(tgt_ptr, tgt_idx, nq, "rank_scores")
+    if tgt_idx.numel() == 0:
+        return torch.full((nq,), nk, dtype=torch.int32, device=scores.device), torch.empty(0, dtype=torch.int32, device=scores.device)
+    rank_row = torch.empty(nq, dtype=torch.int32, device=scores.device)
+    rank_tgt = torch.empty(tgt_idx.numel(), dtype=torch.int32, device=scores.device)
+    _check(load().madtp_rank_scores(_p(scores), ld, nq, nk, _p(tgt_ptr), _p(tgt_idx), _p(rank_row), _p(rank_tgt),
+                                    _stream()), "madtp_rank_scores")
+    return rank_row, rank_tgt

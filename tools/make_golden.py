@@ -1430,6 +1430,101 @@ def clip_train_case(name, B, temperature, idx, cap_lens, alpha=0.4, queue_size=4
           f"losses={rec['losses'].round(5).tolist()} losses2={rec['losses2'].round(5).tolist()} {n} gradients")
 
 
+def clip_eval_case(name, n_img, img_bs, cap, temperature, seed=0, size=96, n_seeds=16, min_gap=1e-4):
+    """compress_retrieval_clip_dtp.py evaluate() and itm_eval() - the reference's own functions, imported behind the shims - on
+    the reference's CLIP (clip/model.py, ViT-B/16 geometry at 96^2 as in clip_train_case, evaluate=True, synthetic weights): n_img
+    images in batches of img_bs, cap captions each (caption j belongs to image j // cap).  As in clip_train_case the kept tokens
+    of every pruning step are put in ascending order (CanonicalTap).  Recorded: the normalised embeddings (the outputs of
+    encode_image / encode_text, captured on their way through evaluate() and normalised as :93 / :101 do), sims, the nine metrics,
+    the per-target ranks and the per-layer lengths of every batch.
+    Gap.  A rank of the recording survives another implementation's rounding only where the ground-truth score is further from
+    every other score of its row (column) than that rounding.  100x the feature tolerance of
+    tests/test_model_parity_gpu.py::test_clip_both_towers (1e-3) would be 0.1, which no seed can give: with synthetic weights
+    the two towers are unrelated and all n_img * n_txt cosine scores lie within ~0.12 of each other.  So every seed of
+    [seed, seed + n_seeds) is run and the one with the LARGEST smallest float64 gap is kept (seeds 0-15: 4e-6 .. 2.0e-4, kept:
+    seed 13 at 1.98e-4); the recorder asserts min_gap = 1e-4 - a thousand times the f32 rounding of a 512-term dot product of
+    unit vectors (~1e-7), so the ranks of the RECORDED embeddings are reproducible exactly by any f32 summation order - and stores
+    the per-target gaps, with which a test decides which ranks of a live model (features within 1e-3) are pinned."""
+    import types
+    import clip.mock  # noqa: F401
+    import clip.model as cm
+    import compress_retrieval_clip_dtp as crc
+    from madtp_amd import specs
+    n_txt = n_img * cap
+    txt2img = [j // cap for j in range(n_txt)]
+    img2txt = [list(range(i * cap, (i + 1) * cap)) for i in range(n_img)]
+    nb = (n_img + img_bs - 1) // img_bs
+
+    def pos(row):
+        order = np.argsort(row, kind="stable")[::-1]
+        p = np.empty(len(order), dtype=np.int64)
+        p[order] = np.arange(len(order))
+        return p
+
+    def record(s):
+        model = cm.CLIP(512, size, 12, 768, 16, 77, 49408, 512, 8, 12, True, None)
+        model.eval()
+        sd = specs.synth_weights(specs.clip_shapes(size), s)
+        msg = model.load_state_dict(sd, strict=False)
+        assert not msg.unexpected_keys, msg.unexpected_keys
+        assert all(k.endswith("_m") or "_m." in k or "queue" in k for k in msg.missing_keys), msg.missing_keys[:8]
+        images = synth.synth_images(n_img, size, s)
+        text = synth.synth_clip_tokens(n_txt, 77, s, 6, 40)
+        model.tokenize = lambda t: t
+
+        class Loader:
+            dataset = types.SimpleNamespace(text=text)
+            def __len__(self): return nb
+            def __iter__(self):
+                for b in range(0, n_img, img_bs):
+                    yield images[b:b + img_bs], ["caption"] * len(images[b:b + img_bs]), torch.arange(b, min(n_img, b + img_bs))
+
+        tap = CanonicalTap(cm)
+        hooks, vlens, tlens, feats = [], [], [], {"img": [], "txt": []}
+        for i, blk in enumerate(model.visual.transformer.resblocks):
+            hooks.append(blk.register_forward_pre_hook(lambda m, a, i=i: tap.set_tag(f"vit{i}")))
+            hooks.append(blk.register_forward_hook(lambda m, a, o: vlens.append(o[0].shape[0])))
+        for i, blk in enumerate(model.transformer.resblocks):
+            hooks.append(blk.register_forward_pre_hook(lambda m, a, i=i: tap.set_tag(f"txt{i}")))
+            hooks.append(blk.register_forward_hook(lambda m, a, o: tlens.append(o[0].shape[0])))
+        enc_i, enc_t = model.encode_image, model.encode_text
+
+        def keep(kind, out):
+            feats[kind].append(out[0].detach().clone())
+            return out
+        model.encode_image = lambda *a, **k: keep("img", enc_i(*a, **k))
+        model.encode_text = lambda *a, **k: keep("txt", enc_t(*a, **k))
+        sims, sims_t, _ = crc.evaluate(model, Loader(), torch.device("cpu"), {"alpha": 0.4}, temperature)
+        metrics = crc.itm_eval(sims, sims_t, txt2img, img2txt)
+        for h in hooks:
+            h.remove()
+        tap.restore()
+        img_e = torch.cat([f / f.norm(dim=1, keepdim=True) for f in feats["img"]], 0)
+        txt_e = torch.cat([f / f.norm(dim=1, keepdim=True) for f in feats["txt"]], 0)
+        assert np.array_equal(sims, (img_e @ txt_e.t()).numpy()) and np.array_equal(sims_t, sims.T)
+        s64 = (img_e.double() @ txt_e.double().t()).numpy()
+        gap_i2t = np.array([np.abs(np.delete(s64[txt2img[j]], j) - s64[txt2img[j], j]).min() for j in range(n_txt)])
+        gap_t2i = np.array([np.abs(np.delete(s64[:, j], txt2img[j]) - s64[txt2img[j], j]).min() for j in range(n_txt)])
+        gap = float(min(gap_i2t.min(), gap_t2i.min()))
+        rank_tgt_i2t = np.array([pos(sims[i])[j] for i in range(n_img) for j in img2txt[i]], dtype=np.int32)
+        rank_tgt_t2i = np.array([pos(sims_t[j])[txt2img[j]] for j in range(n_txt)], dtype=np.int32)
+        assert len(vlens) == 12 * nb and len(tlens) == 12, (len(vlens), len(tlens))
+        rec = {"kind": "clip_eval", "n_img": n_img, "img_bs": img_bs, "cap": cap, "size": size, "temperature": np.float64(temperature),
+               "seed": s, "gap": np.float64(gap), "gap_i2t": gap_i2t, "gap_t2i": gap_t2i, "image_embeds": img_e.numpy(),
+               "text_embeds": txt_e.numpy(), "sims": sims, "txt2img": np.array(txt2img, dtype=np.int32),
+               "rank_tgt_i2t": rank_tgt_i2t, "rank_tgt_t2i": rank_tgt_t2i, "rank_row_i2t": rank_tgt_i2t.reshape(n_img, cap).min(1),
+               "metric_names": np.array(sorted(metrics)), "metrics": np.array([metrics[k] for k in sorted(metrics)], dtype=np.float64),
+               "vit_lens": np.array(vlens).reshape(nb, 12), "txt_lens": np.array(tlens).reshape(1, 12)}
+        print(f"[{name}] seed {s}: smallest gap around a ground-truth score {gap:.3e}")
+        return rec
+
+    best = max((record(s) for s in range(seed, seed + n_seeds)), key=lambda r: float(r["gap"]))
+    assert float(best["gap"]) >= min_gap, f"largest gap over seeds [{seed}, {seed + n_seeds}) is {float(best['gap']):.3e} < {min_gap}"
+    np.savez_compressed(os.path.join(GOLD, name + ".npz"), **best)
+    print(f"[{name}] T={temperature} kept seed {int(best['seed'])} gap {float(best['gap']):.3e} vit_lens={best['vit_lens'].tolist()} "
+          f"txt_lens={best['txt_lens'].tolist()} metrics={dict(zip(best['metric_names'].tolist(), best['metrics'].round(2).tolist()))}")
+
+
 L14 = dict(patch=14, vision_width=1024, vision_layers=24, embed_dim=768, text_width=768)
 
 CASES = {
@@ -1497,6 +1592,8 @@ CASES = {
     "modelgrad_nlvr_b2": lambda: nlvr_model_grad_case("modelgrad_nlvr_b2", 2, 96, 35, 30.0, pad_tail=0, nsample=64),
     "nlvrgrad_b3_l3": lambda: nlvr_layer_grad_case("nlvrgrad_b3_l3", 3, 35, 30.0, layer=3, pad_tail=3),
     "nlvrgrad_b3_l7": lambda: nlvr_layer_grad_case("nlvrgrad_b3_l7", 3, 35, 30.0, layer=7, pad_tail=3),
+    # the CLIP driver's evaluate() + itm_eval(): 6 images in batches of 4 + 2, 3 captions each
+    "clipeval_b6_T4": lambda: clip_eval_case("clipeval_b6_T4", 6, 4, 3, 4.0),
     "medgrad_mm_b3_l3": lambda: med_layer_grad_case("medgrad_mm_b3_l3", 3, 35, 30.0, layer=3, pad_tail=3, mode="multimodal", Nimg=50),
 }
 
