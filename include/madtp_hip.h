@@ -206,6 +206,41 @@ int madtp_attention_pair(const void* q0, const void* q1, const void* k0, const v
                          int B, int H, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, float scale, int io_dtype,
                          void* stream);
 
+/* The dispatch decision madtp_attention / madtp_attention_qk_mask / madtp_attention_indexed (flags without MADTP_ATTN_PLAN_PAIR) or
+ * madtp_attention_pair (with it) takes for a problem, without launching: no HIP call, nothing allocated.  `flags` carries what the
+ * decision reads beside the sizes; every pointer counts as present and 16-byte aligned unless a flag says otherwise.  `resources`:
+ * which device scratch areas can be had (a launch falls back to the plan without one whose allocation fails).  kv_block_rows and
+ * split_req are arguments of the library's internal layer calls (0 for the exported entries): rows from one sample's K/V block to the
+ * next, and the column offset of the second f16-split plane of a context written as planes.  Writes MADTP_ATTN_PLAN_FIELDS int32
+ * into plan (plan_len >= MADTP_ATTN_PLAN_FIELDS):
+ *   status (0, a MADTP_E_* code, or 1000 = this pair runs as two launches; then family is -1 and the rest 0),
+ *   family (0 attn_kernel, 1 attn_f16s_kernel, 2 attn_bf16_kernel, 3 attn_bf16_small_kernel, 4 attn_large_kernel,
+ *   5 attn_large_f16s_kernel, 6 attn_bf16_large_kernel), key capacity of the instantiation (16-key tiles up to 256 keys, 128-key
+ *   chunks beyond), storage type of families 0 and 4 (0 f32, 1 bf16), with scores, f16 operands, head-parity split, 64-row blocks
+ *   per workgroup, sweep order (2 = three sweeps), grid x, y, z, workgroup size, dynamic LDS bytes, LDS bytes the instantiation is
+ *   opted in to, needs the head-max exchange area, needs the three-sweep scratch, split-plane column offset.
+ * MADTP_E_BADARG: plan is NULL or plan_len too small. */
+#define MADTP_ATTN_PLAN_PAIR 1
+#define MADTP_ATTN_PLAN_SCORES 2            /* colsum_part given */
+#define MADTP_ATTN_PLAN_MASK_QK 4
+#define MADTP_ATTN_PLAN_ADD_MASK 8
+#define MADTP_ATTN_PLAN_KV_INDEX 16
+#define MADTP_ATTN_PLAN_N_DEV 32            /* token count read on the device (internal sync-free encoder path) */
+#define MADTP_ATTN_PLAN_DEV_Q_ONLY 64       /* ... of the query tokens only */
+#define MADTP_ATTN_PLAN_NULL_PTR 128        /* one of q, k, v, out is NULL */
+#define MADTP_ATTN_PLAN_NO_P0 256
+#define MADTP_ATTN_PLAN_NO_ONORM 512
+#define MADTP_ATTN_PLAN_QKV_UNALIGNED 1024  /* one of q, k, v is not 16-byte aligned */
+#define MADTP_ATTN_PLAN_OUT_UNALIGNED16 2048
+#define MADTP_ATTN_PLAN_OUT_UNALIGNED8 4096
+#define MADTP_ATTN_PLAN_PAIR_UNALIGNED 8192 /* one of the second problem's q, k, v is not 16-byte aligned */
+#define MADTP_ATTN_PLAN_PAIR_MASKS_DIFFER 16384 /* one problem of the pair has an additive mask, the other has none */
+#define MADTP_ATTN_RES_HM 1    /* resources: the head-max exchange area */
+#define MADTP_ATTN_RES_OPART 2 /* resources: the three-sweep scratch */
+#define MADTP_ATTN_PLAN_FIELDS 18
+int madtp_attention_plan(int B, int H, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, int io_dtype, int ld_mask_qk, int kv_block_rows,
+                         int split_req, int flags, int resources, int32_t* plan, int plan_len);
+
 /* Alignment-guided token-importance score, per-sample threshold and survivor count
  * (Block.Reduce_token vit.py:125-145 == med.py:347-371 == nlvr_encoder.py:404-432 == clip/model.py:196-218).
  * n = N-1 patch tokens.  token_attn f32: element [b,t,c] at token_attn[b*ldt_batch + t*ldt_row + c], c < K (raw

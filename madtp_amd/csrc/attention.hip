@@ -19,9 +19,11 @@
 // other query tiles of the same b hit L2).
 #include "common.h"
 #include "internal.h"
+#include "attn_plan.h"  // the dispatch policy (host)
 #include <map>
 #include <mutex>
 #include <stdlib.h>
+#include <string.h>
 
 namespace {
 
@@ -59,12 +61,9 @@ struct AttnArgs {
         (a).nrt = ((a).Nq + 15) / 16;                      \
     }
 
-// Exchange area of the head split (one per device and stream, allocated on first use; the tickets reset themselves).
+// Exchange area of the head split (attn_plan.h HM_MAX_*; one per device and stream, allocated on first use; the tickets reset themselves).
 struct HmWorkspace { unsigned* ws; int* tick; };
-constexpr int HM_MAX_WGS = 384, HM_MAX_NT = 40, HM_MAX_GZ = 4;  // (attn_bf16_large_kernel splits the heads over up to 4 workgroups)
 static bool hm_workspace(hipStream_t s, HmWorkspace& out) {
-    static const int env = env_int("MADTP_ATTN_HEAD_SPLIT", 1);
-    if (!env) return false;
     static std::mutex mu;
     static std::map<std::pair<int, hipStream_t>, HmWorkspace> pool;
     int dev = 0;
@@ -294,7 +293,7 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnArgs a) {
 
     if constexpr (SCORES) {
         if (gridDim.z == 2) {
-            // two workgroups per row block, half of the heads each (launch_attn): the head-max halves are merged by the wave that
+            // two workgroups per row block, half of the heads each (attn_plan.h): the head-max halves are merged by the wave that
             // arrives second - a max of the same f32 values, so the column sums are bit-identical to the one-workgroup launch
             // (protocol: attn_bf16_large_kernel)
             const size_t slot = ((size_t)b * gridDim.x + blockIdx.x) * 4 + wave;
@@ -894,6 +893,7 @@ __global__ __launch_bounds__(256 * HS * RB, (HS == 1 && RB == 1) ? 2 : 1) void a
 // SMALL_NW waves per workgroup: with 12 heads every wave owns exactly one head (a head is a ~3 us dependent chain; four
 // waves walking three heads each made the kernel three chains long).
 constexpr int SMALL_NW = 12;
+static_assert(SMALL_NW == ATTN_SMALL_NW, "attn_plan.h sizes the workgroup of attn_bf16_small_kernel");
 template <bool F16>
 __global__ __launch_bounds__(64 * SMALL_NW, 1) void attn_bf16_small_kernel(AttnArgs a) {
     __shared__ __attribute__((aligned(16))) char vbuf[SMALL_NW][32 * 128];
@@ -1038,42 +1038,6 @@ __global__ __launch_bounds__(64 * SMALL_NW, 1) void attn_bf16_small_kernel(AttnA
                 if (l16 == 0 && j < N) dst[j] = v;
             }
     }
-}
-
-template <int NT, bool SCORES, bool F16>
-int launch_attn_bf16(const AttnArgs& a, hipStream_t s) {
-    constexpr int NC = (NT + 1) / 2;
-    constexpr int HS = (SCORES && NT <= 8) ? 2 : 1;  // head-parity split: 4 rings must fit the 160 KiB of LDS
-    constexpr int RB = (SCORES && NT > 8) ? 2 : 1;   // two 64-row blocks per workgroup where only one ring fits a CU
-    const size_t lds = (size_t)2 * HS * (NT * 16 + NC * 32) * 128;
-    MADTP_ENSURE_MAX_LDS((attn_bf16_kernel<NT, SCORES, HS, RB, F16>), lds);
-    int gz = 1;
-    size_t lds_used = lds;
-    if (!SCORES) {
-        // cross-attention (few query rows per sample): below 512 workgroups every head gets its own workgroup - no head loop,
-        // so ONE ring stage is allocated and 2-6 workgroups share a CU (the two-stage ring of a 190-key problem is 98 KiB,
-        // one 4-wave workgroup per CU)
-        const int wgs = ((a.Nq + 63) / 64) * a.B;
-        gz = wgs >= 512 ? 1 : a.H;
-        if (gz == a.H) lds_used = lds / 2;
-    }
-    hipLaunchKernelGGL((attn_bf16_kernel<NT, SCORES, HS, RB, F16>), dim3((a.Nq + 64 * RB - 1) / (64 * RB), (!SCORES && a.pair) ? 2 * a.B : a.B, gz),
-                       dim3(256 * HS * RB), lds_used, s, a);
-    MADTP_LAUNCH_CHECK();
-    return 0;
-}
-
-template <bool SCORES, bool F16 = false>
-int dispatch_nt_bf16(const AttnArgs& a, hipStream_t s) {
-    const int nt = (a.Nk + 15) / 16;
-    if (nt <= 4) return launch_attn_bf16<4, SCORES, F16>(a, s);
-    if (nt <= 6) return launch_attn_bf16<6, SCORES, F16>(a, s);
-    if (nt <= 8) return launch_attn_bf16<8, SCORES, F16>(a, s);
-    if (nt <= 10) return launch_attn_bf16<10, SCORES, F16>(a, s);
-    if (nt <= 12) return launch_attn_bf16<12, SCORES, F16>(a, s);
-    if (nt <= 13) return launch_attn_bf16<13, SCORES, F16>(a, s);
-    if (nt <= 16) return launch_attn_bf16<16, SCORES, F16>(a, s);
-    return MADTP_E_SHAPE;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1489,45 +1453,6 @@ __global__ __launch_bounds__(256, 1) void attn_large_f16s_kernel(AttnArgs a) {  
     }
 }
 
-template <int NCH, bool SCORES>
-int launch_attn_large_f16s(const AttnArgs& a, hipStream_t s) {
-    const size_t lds = (size_t)4 * 128 * 160;
-    MADTP_ENSURE_MAX_LDS((attn_large_f16s_kernel<NCH, SCORES>), lds);
-    int gz = 1;
-    if (!SCORES) {
-        const int wgs = ((a.Nq + 63) / 64) * a.B;
-        gz = wgs >= 512 ? 1 : (wgs >= 128 ? 4 : a.H);
-        if (gz > a.H) gz = a.H;
-    }
-    hipLaunchKernelGGL((attn_large_f16s_kernel<NCH, SCORES>), dim3((a.Nq + 63) / 64, a.B, gz), dim3(256), lds, s, a);
-    MADTP_LAUNCH_CHECK();
-    return 0;
-}
-
-template <bool SCORES>
-int dispatch_large_f16s(const AttnArgs& a, hipStream_t s) {
-    const int nch = (a.Nk + 127) / 128;
-    if (nch <= 5) return launch_attn_large_f16s<5, SCORES>(a, s);
-    if (nch <= 8) return launch_attn_large_f16s<8, SCORES>(a, s);
-    return MADTP_E_SHAPE;
-}
-
-template <typename T, int NCH, bool SCORES>
-int launch_attn_large(const AttnArgs& a, hipStream_t s) {
-    constexpr int RB = 64 * (int)sizeof(T) + 16;
-    const size_t lds = (size_t)2 * 128 * RB;
-    MADTP_ENSURE_MAX_LDS((attn_large_kernel<T, NCH, SCORES>), lds);
-    int gz = 1;
-    if (!SCORES) {
-        const int wgs = ((a.Nq + 63) / 64) * a.B;
-        gz = wgs >= 512 ? 1 : (wgs >= 128 ? 4 : a.H);
-        if (gz > a.H) gz = a.H;
-    }
-    hipLaunchKernelGGL((attn_large_kernel<T, NCH, SCORES>), dim3((a.Nq + 63) / 64, a.B, gz), dim3(256), lds, s, a);
-    MADTP_LAUNCH_CHECK();
-    return 0;
-}
-
 // ------------------------------------------------------------------------------------------------------------------
 // bf16 fast-mode kernel for long sequences (256 < Nk <= 1024).  Same two passes per head as attn_large_kernel (the head-max
 // of the NORMALISED probabilities needs a row's final max / sum before any probability can be compared across heads), but
@@ -1541,7 +1466,7 @@ int launch_attn_large(const AttnArgs& a, hipStream_t s) {
 // two 4-wave workgroups per CU up to 640 keys (the 1024-key instantiation would spill at 256 registers and keeps one).
 // Work per (b, h): 6 Nq Nk 64 flop (Q K^T twice) on the bf16 MFMA; the bound is the VALU softmax work (2 exp per score, each
 // one fma + v_exp_f32 on the unscaled score, see scores()).
-// STG: stages of the chunk ring (2 is what launch_attn_bf16_large uses; 3 keeps two chunks in flight behind counted vmcnt waits
+// STG: stages of the chunk ring (2 is what every launch uses, attn_plan.h; 3 keeps two chunks in flight behind counted vmcnt waits
 // and was measured slower, see there).
 // HV = 2 (round 5, the 641..1024-key instantiation with scores: VQA's 901 tokens): the head-max of all 64 key tiles is 128
 // registers and pinned the kernel at ONE wave per SIMD (318 registers; a chunk step of a lone wave is bound by its own dependent
@@ -1983,7 +1908,7 @@ __global__ __launch_bounds__(256, (STG == 2 && (NCH <= 5 || !SCORES || HV == 2))
     }
     if constexpr (SCORES) {
         if (ngz >= 2) {
-            // gridDim.z workgroups (2..4) share this row block, each with a share of the heads (launch_attn_bf16_large: launches
+            // gridDim.z workgroups (2..4) share this row block, each with a share of the heads (attn_plan.h: launches
             // that would leave most SIMDs with one wave or none, or whose round count a finer split lowers).  The head-max is a max
             // - exact and order-free - so the shares are merged by whichever wave arrives LAST: agent-scope stores / loads (written
             // through and read past the L2s: the workgroups may sit on different XCDs) around one agent-scope ticket per (row
@@ -2046,145 +1971,142 @@ static float* opart_workspace(hipStream_t s, size_t bytes) {
     return (float*)e.first;
 }
 
-template <int NCH, bool SCORES, bool F16>
-int launch_attn_bf16_large(const AttnArgs& a_in, hipStream_t s) {
-    AttnArgs a = a_in;
-    int gz = 1;
-    if constexpr (SCORES && NCH == 8) {
-        // 641..1024 keys with scores: the three-sweep order (HV = 2), two workgroups per CU (MADTP_ATTN_HV=0: the one-sweep order)
-        static const int hv_env = env_int("MADTP_ATTN_HV", 1);
-        if (hv_env && a.H <= 16 && (a.Nk + 127) / 128 > NCH / 2) {
-            float* op = opart_workspace(s, (size_t)a.B * a.Nq * a.H * 64 * sizeof(float));
-            if (op) {
-                a.o_part = op;
-                const size_t lds2 = (size_t)2 * 2 * 128 * 128 + 4 * 2048 + (size_t)a.H * 128 * sizeof(float);
-                MADTP_ENSURE_MAX_LDS((attn_bf16_large_kernel<NCH, true, 2, F16, 2>), lds2);
-                hipLaunchKernelGGL((attn_bf16_large_kernel<NCH, true, 2, F16, 2>), dim3((a.Nq + 63) / 64, a.B, 1), dim3(256), lds2, s, a);
-                MADTP_LAUNCH_CHECK();
-                return 0;
-            }
-        }
-    }
-    const int wgs = ((a.Nq + 63) / 64) * a.B;
-    if (!SCORES) {  // cross-attention against a long image sequence: few query rows, spread the heads over workgroups
-        gz = wgs >= 512 ? 1 : (wgs >= 128 ? 4 : a.H);
-        if (gz > a.H) gz = a.H;
-    } else if (NCH * 8 <= HM_MAX_NT && wgs <= HM_MAX_WGS && a.H % 2 == 0) {
-        // With scores a row block walks all heads (the head-max).  B x ceil(N/64) <= 256 workgroups of four waves leave the
-        // 1024 SIMDs with one wave or none (VQA: 32 x 7), each bound by its own dependent instruction stream: 2..4 workgroups
-        // per row block take a share of the heads each and merge their head-max at the end (MADTP_ATTN_HEAD_SPLIT=0: off).
-        // The split that minimises rounds x heads per workgroup (512 workgroup slots at two per CU, 256 at one): e.g. 32 samples
-        // x 605 keys = 320 row blocks: 2 groups = 640 workgroups = 2 rounds x 6 heads, 3 groups = 960 = 2 rounds x 4 heads.
-        HmWorkspace hw;
-        if (hm_workspace(s, hw)) {
-            const int cap = 256 * ((NCH <= 5) ? 2 : 1);
-            int best = 2, best_cost = 1 << 30;
-            for (int z = 2; z <= HM_MAX_GZ; ++z) {
-                if (a.H % z) continue;
-                const int cost = ((wgs * z + cap - 1) / cap) * (a.H / z);
-                if (cost < best_cost) { best_cost = cost; best = z; }
-            }
-            static const int gz_env = env_int("MADTP_ATTN_HEAD_GROUPS", 0);  // 2..4 forces the split (A/B runs)
-            if (gz_env >= 2 && gz_env <= HM_MAX_GZ && a.H % gz_env == 0) best = gz_env;
-            gz = best; a.hm_ws = hw.ws; a.hm_tick = hw.tick;
-        }
-    }
-    const dim3 grid((a.Nq + 63) / 64, a.B, gz);
-    // Two stages.  The three-stage ring (STG = 3: two chunks in flight behind counted vmcnt waits, 104 KiB, one workgroup per
-    // CU) was measured 4-8 % SLOWER at one workgroup per CU and 40 % slower where two would fit (tools/attn_large_bench.py): a
-    // chunk step of a lone wave is bound by its own dependent instruction stream (~1.85 us against ~1.2 us with two waves per
-    // SIMD), not by the DMA round trip.
-    const size_t lds = (size_t)2 * 2 * 128 * 128 + 4 * 2048;  // two stages of K|V chunk images + the waves' Q rows
-    MADTP_ENSURE_MAX_LDS((attn_bf16_large_kernel<NCH, SCORES, 2, F16>), lds);
-    hipLaunchKernelGGL((attn_bf16_large_kernel<NCH, SCORES, 2, F16>), grid, dim3(256), lds, s, a);
+// The process switches of the dispatch (attn_plan.h AttnSwitches), read from the environment once.
+static const AttnSwitches& attn_switches() {
+    static const AttnSwitches sw = [] {
+        AttnSwitches e;
+        e.head_split = env_int("MADTP_ATTN_HEAD_SPLIT", e.head_split);
+        e.hv = env_int("MADTP_ATTN_HV", e.hv);
+        e.head_groups = env_int("MADTP_ATTN_HEAD_GROUPS", e.head_groups);
+        e.f16s = env_int("MADTP_ATTN_F16S", e.f16s);
+        e.large_f32 = env_int("MADTP_ATTN_LARGE_F32", e.large_f32);
+        e.pair = env_int("MADTP_ATTN_PAIR", e.pair);
+        return e;
+    }();
+    return sw;
+}
+
+// One launch per kernel instantiation (the LDS opt-in of MADTP_ENSURE_MAX_LDS is remembered per instantiation).
+template <void (*KERNEL)(AttnArgs)>
+int attn_launch_kernel(const AttnArgs& a, const AttnPlan& pl, hipStream_t s) {
+    if (pl.lds_optin) MADTP_ENSURE_MAX_LDS(KERNEL, pl.lds_optin);
+    hipLaunchKernelGGL(KERNEL, dim3(pl.gx, pl.gy, pl.gz), dim3(pl.block), pl.lds, s, a);
     MADTP_LAUNCH_CHECK();
     return 0;
 }
 
-template <bool SCORES, bool F16 = false>
-int dispatch_bf16_large(const AttnArgs& a, hipStream_t s) {
-    const int nch = (a.Nk + 127) / 128;
-    if (nch <= 3) return launch_attn_bf16_large<3, SCORES, F16>(a, s);
-    if (nch <= 5) return launch_attn_bf16_large<5, SCORES, F16>(a, s);
-    if (nch <= 8) return launch_attn_bf16_large<8, SCORES, F16>(a, s);
-    return MADTP_E_SHAPE;
-}
-
-template <typename T, bool SCORES>
-int dispatch_large(const AttnArgs& a, hipStream_t s) {
-    const int nch = (a.Nk + 127) / 128;
-    if (nch <= 5) return launch_attn_large<T, 5, SCORES>(a, s);
-    if (nch <= 8) return launch_attn_large<T, 8, SCORES>(a, s);
-    return MADTP_E_SHAPE;
-}
-
-template <typename T, int NT, bool SCORES>
-int launch_attn(const AttnArgs& a_in, hipStream_t s) {
-    constexpr int RB = 64 * (int)sizeof(T) + 16;
-    const size_t lds = (size_t)2 * NT * 16 * RB;
-    MADTP_ENSURE_MAX_LDS((attn_kernel<T, NT, SCORES>), lds);
-    int gz = 1;
-    AttnArgs a = a_in;
-    const int wgs = ((a.Nq + 63) / 64) * a.B;
-    if (!SCORES) {  // cross-attention has few query rows: spread heads over workgroups
-        gz = wgs >= 512 ? 1 : (wgs >= 128 ? 4 : a.H);
-        if (gz > a.H) gz = a.H;
-    } else if (4 * NT <= 2 * HM_MAX_NT && wgs <= HM_MAX_WGS && a.H % 2 == 0) {
-        // with scores a row block walks all heads: a launch that leaves the SIMDs with one wave or none (128 images x 2 row
-        // blocks in the parity modes, 64 text samples) runs two workgroups per row block, half of the heads each
-        HmWorkspace hw;
-        if (hm_workspace(s, hw)) { gz = 2; a.hm_ws = hw.ws; a.hm_tick = hw.tick; }
-    }
-    hipLaunchKernelGGL((attn_kernel<T, NT, SCORES>), dim3((a.Nq + 63) / 64, a.B, gz), dim3(256), lds, s, a);
-    MADTP_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int NT, bool SCORES>
-int launch_attn_f16s(const AttnArgs& a_in, hipStream_t s) {
-    constexpr int PITCH = NT <= 15 ? 160 : 144;
-    const size_t lds = (size_t)(2 * NT * 16 + 2 * ((NT + 1) / 2) * 32) * PITCH;
-    MADTP_ENSURE_MAX_LDS((attn_f16s_kernel<NT, SCORES>), lds);
-    int gz = 1;
-    AttnArgs a = a_in;
-    const int wgs = ((a.Nq + 63) / 64) * a.B;
-    if (!SCORES) {
-        gz = wgs >= 512 ? 1 : (wgs >= 128 ? 4 : a.H);
-        if (gz > a.H) gz = a.H;
-    } else if (4 * NT <= 2 * HM_MAX_NT && wgs <= HM_MAX_WGS && a.H % 2 == 0) {
-        HmWorkspace hw;
-        if (hm_workspace(s, hw)) { gz = 2; a.hm_ws = hw.ws; a.hm_tick = hw.tick; }
-    }
-    hipLaunchKernelGGL((attn_f16s_kernel<NT, SCORES>), dim3((a.Nq + 63) / 64, a.B, gz), dim3(256), lds, s, a);
-    MADTP_LAUNCH_CHECK();
-    return 0;
-}
-
+// Plan -> template instance.  Every instantiation the library contains is named here once: a key capacity that a family's ladder
+// (attn_plan.h) does not have is no case, so nothing else is compiled.
+#define ATTN_CASE(N, ...) case N: return attn_launch_kernel<__VA_ARGS__>(a, pl, s);
 template <bool SCORES>
-int dispatch_nt_f16s(const AttnArgs& a, hipStream_t s) {
-    const int nt = (a.Nk + 15) / 16;
-    if (nt <= 2) return launch_attn_f16s<2, SCORES>(a, s);
-    if (nt <= 4) return launch_attn_f16s<4, SCORES>(a, s);
-    if (nt <= 6) return launch_attn_f16s<6, SCORES>(a, s);
-    if (nt <= 8) return launch_attn_f16s<8, SCORES>(a, s);
-    if (nt <= 10) return launch_attn_f16s<10, SCORES>(a, s);
-    if (nt <= 13) return launch_attn_f16s<13, SCORES>(a, s);
-    if (nt <= 16) return launch_attn_f16s<16, SCORES>(a, s);
+int attn_launch_f32(const AttnArgs& a, const AttnPlan& pl, hipStream_t s) {  // the exact-f32 MFMA and the f16x3 families
+    switch (pl.family) {
+    case ATTN_KERNEL:
+        switch (pl.nt) {
+            ATTN_CASE(2, attn_kernel<float, 2, SCORES>) ATTN_CASE(4, attn_kernel<float, 4, SCORES>) ATTN_CASE(6, attn_kernel<float, 6, SCORES>)
+            ATTN_CASE(8, attn_kernel<float, 8, SCORES>) ATTN_CASE(10, attn_kernel<float, 10, SCORES>) ATTN_CASE(12, attn_kernel<float, 12, SCORES>)
+            ATTN_CASE(13, attn_kernel<float, 13, SCORES>) ATTN_CASE(16, attn_kernel<float, 16, SCORES>)
+        }
+        break;
+    case ATTN_F16S_KERNEL:
+        switch (pl.nt) {
+            ATTN_CASE(2, attn_f16s_kernel<2, SCORES>) ATTN_CASE(4, attn_f16s_kernel<4, SCORES>) ATTN_CASE(6, attn_f16s_kernel<6, SCORES>)
+            ATTN_CASE(8, attn_f16s_kernel<8, SCORES>) ATTN_CASE(10, attn_f16s_kernel<10, SCORES>) ATTN_CASE(13, attn_f16s_kernel<13, SCORES>)
+            ATTN_CASE(16, attn_f16s_kernel<16, SCORES>)
+        }
+        break;
+    case ATTN_LARGE_KERNEL:
+        switch (2 * pl.nt + pl.storage) {
+            ATTN_CASE(2 * 5, attn_large_kernel<float, 5, SCORES>) ATTN_CASE(2 * 8, attn_large_kernel<float, 8, SCORES>)
+            ATTN_CASE(2 * 5 + 1, attn_large_kernel<bf16_t, 5, SCORES>) ATTN_CASE(2 * 8 + 1, attn_large_kernel<bf16_t, 8, SCORES>)
+        }
+        break;
+    case ATTN_LARGE_F16S_KERNEL:
+        switch (pl.nt) { ATTN_CASE(5, attn_large_f16s_kernel<5, SCORES>) ATTN_CASE(8, attn_large_f16s_kernel<8, SCORES>) }
+        break;
+    }
     return MADTP_E_SHAPE;
 }
-
-template <typename T, bool SCORES>
-int dispatch_nt(const AttnArgs& a, hipStream_t s) {
-    const int nt = (a.Nk + 15) / 16;
-    if (nt <= 2) return launch_attn<T, 2, SCORES>(a, s);  // <= 32 keys: the text encoder's self-attention (20-35 tokens)
-    if (nt <= 4) return launch_attn<T, 4, SCORES>(a, s);
-    if (nt <= 6) return launch_attn<T, 6, SCORES>(a, s);  // 81-96 keys: nine of the twelve ViT layers of the headline workload
-    if (nt <= 8) return launch_attn<T, 8, SCORES>(a, s);
-    if (nt <= 10) return launch_attn<T, 10, SCORES>(a, s);
-    if (nt <= 12) return launch_attn<T, 12, SCORES>(a, s);
-    if (nt <= 13) return launch_attn<T, 13, SCORES>(a, s);
-    if (nt <= 16) return launch_attn<T, 16, SCORES>(a, s);
+template <int NT, bool SCORES, bool F16>
+constexpr auto attn_bf16_instance = attn_bf16_kernel<NT, SCORES, attn_bf16_hs(SCORES, NT), attn_bf16_rb(SCORES, NT), F16>;
+template <bool SCORES, bool F16>
+int attn_launch_lp(const AttnArgs& a, const AttnPlan& pl, hipStream_t s) {  // the bf16 / f16 MFMA families
+    switch (pl.family) {
+    case ATTN_BF16_KERNEL:
+        switch (pl.nt) {
+            ATTN_CASE(4, attn_bf16_instance<4, SCORES, F16>) ATTN_CASE(6, attn_bf16_instance<6, SCORES, F16>) ATTN_CASE(8, attn_bf16_instance<8, SCORES, F16>)
+            ATTN_CASE(10, attn_bf16_instance<10, SCORES, F16>) ATTN_CASE(12, attn_bf16_instance<12, SCORES, F16>)
+            ATTN_CASE(13, attn_bf16_instance<13, SCORES, F16>) ATTN_CASE(16, attn_bf16_instance<16, SCORES, F16>)
+        }
+        break;
+    case ATTN_BF16_SMALL_KERNEL:
+        if constexpr (SCORES) return attn_launch_kernel<attn_bf16_small_kernel<F16>>(a, pl, s);
+        break;
+    case ATTN_BF16_LARGE_KERNEL:
+        if constexpr (SCORES)
+            if (pl.hv == 2) {
+                if (pl.nt == 8) return attn_launch_kernel<attn_bf16_large_kernel<8, true, 2, F16, 2>>(a, pl, s);
+                break;
+            }
+        switch (pl.nt) {
+            ATTN_CASE(3, attn_bf16_large_kernel<3, SCORES, 2, F16>) ATTN_CASE(5, attn_bf16_large_kernel<5, SCORES, 2, F16>)
+            ATTN_CASE(8, attn_bf16_large_kernel<8, SCORES, 2, F16>)
+        }
+        break;
+    }
     return MADTP_E_SHAPE;
+}
+#undef ATTN_CASE
+
+int attn_launch(const AttnArgs& a, const AttnPlan& pl, hipStream_t s) {
+    if (pl.family == ATTN_BF16_KERNEL || pl.family == ATTN_BF16_SMALL_KERNEL || pl.family == ATTN_BF16_LARGE_KERNEL) {
+        if (pl.f16) return pl.scores ? attn_launch_lp<true, true>(a, pl, s) : attn_launch_lp<false, true>(a, pl, s);
+        return pl.scores ? attn_launch_lp<true, false>(a, pl, s) : attn_launch_lp<false, false>(a, pl, s);
+    }
+    return pl.scores ? attn_launch_f32<true>(a, pl, s) : attn_launch_f32<false>(a, pl, s);
+}
+
+// Plan, fetch the scratch areas the plan names, launch.  An area that cannot be had is planned without (once per stream at most).
+int attn_run(const AttnProblem& p, AttnArgs& a, hipStream_t s) {
+    AttnResources res;
+    for (;;) {
+        const AttnPlan pl = attn_plan(p, attn_switches(), res);
+        if (pl.status) return pl.status;
+        if (pl.need_hm) {
+            HmWorkspace hw;
+            if (!hm_workspace(s, hw)) { res.hm = false; continue; }
+            a.hm_ws = hw.ws; a.hm_tick = hw.tick;
+        }
+        if (pl.need_opart) {
+            a.o_part = opart_workspace(s, (size_t)a.B * a.Nq * a.H * 64 * sizeof(float));
+            if (!a.o_part) { res.opart = false; continue; }
+        }
+        a.split_dim = pl.split_dim;
+        a.range_flag = pl.split_dim ? madtp_internal_range_flag() : nullptr;
+        return attn_launch(a, pl, s);
+    }
+}
+
+// The planner's input for a problem of this shape; every pointer counts as present and aligned until the caller says otherwise.
+AttnProblem attn_problem(int B, int H, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, int io_dtype, int split_req) {
+    AttnProblem p{};
+    p.B = B; p.H = H; p.Nq = Nq; p.Nk = Nk; p.ldq = ldq; p.ldk = ldk; p.ldv = ldv; p.ldo = ldo;
+    p.io_dtype = io_dtype; p.split_req = split_req;
+    p.ptrs = p.p0 = p.onorm = p.qkv_aligned = p.out_aligned16 = p.out_aligned8 = p.pair_aligned = p.pair_masks_alike = true;
+    return p;
+}
+
+// One problem without side outputs, no scratch areas yet
+AttnArgs attn_args(const void* q, const void* k, const void* v, void* out, const float* add_mask, const int32_t* kv_batch_index, int B, int H, int Nq,
+                   int Nk, int ldq, int ldk, int ldv, int ldo, float scale) {
+    AttnArgs a{};
+    a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.out = (char*)out; a.mask = add_mask;
+    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
+    a.nrt = (Nq + 15) / 16;
+    a.scale = scale;
+    a.kvidx = kv_batch_index;
+    a.kvb = Nk;
+    return a;
 }
 
 }  // namespace
@@ -2243,9 +2165,25 @@ extern "C" int madtp_attention_qk_mask(const void* q, const void* k, const void*
                                     ldv, ldo, scale, io_dtype, 0, stream);
 }
 
-bool madtp_internal_attn_f16s_enabled() {
-    static const int f16s_env = env_int("MADTP_ATTN_F16S", 1);  // 0: the f16x3 mode keeps its attention on the exact-f32 MFMA kernels (A/B runs)
-    return f16s_env != 0;
+bool madtp_internal_attn_f16s_enabled() { return attn_switches().f16s != 0; }
+
+extern "C" int madtp_attention_plan(int B, int H, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, int io_dtype, int ld_mask_qk,
+                                    int kv_block_rows, int split_req, int flags, int resources, int32_t* plan, int plan_len) {
+    if (!plan || plan_len < MADTP_ATTN_PLAN_FIELDS) return MADTP_E_BADARG;
+    AttnProblem p = attn_problem(B, H, Nq, Nk, ldq, ldk, ldv, ldo, io_dtype, split_req);
+    p.pair = flags & MADTP_ATTN_PLAN_PAIR; p.scores = flags & MADTP_ATTN_PLAN_SCORES;
+    p.mask_qk = flags & MADTP_ATTN_PLAN_MASK_QK; p.ld_mask_qk = ld_mask_qk; p.add_mask = flags & MADTP_ATTN_PLAN_ADD_MASK;
+    p.kv_index = flags & MADTP_ATTN_PLAN_KV_INDEX; p.kv_block_rows = kv_block_rows;
+    p.n_dev = flags & MADTP_ATTN_PLAN_N_DEV; p.dev_q_only = flags & MADTP_ATTN_PLAN_DEV_Q_ONLY;
+    p.ptrs = !(flags & MADTP_ATTN_PLAN_NULL_PTR); p.p0 = !(flags & MADTP_ATTN_PLAN_NO_P0); p.onorm = !(flags & MADTP_ATTN_PLAN_NO_ONORM);
+    p.qkv_aligned = !(flags & MADTP_ATTN_PLAN_QKV_UNALIGNED); p.out_aligned16 = !(flags & MADTP_ATTN_PLAN_OUT_UNALIGNED16);
+    p.out_aligned8 = !(flags & MADTP_ATTN_PLAN_OUT_UNALIGNED8); p.pair_aligned = !(flags & MADTP_ATTN_PLAN_PAIR_UNALIGNED);
+    p.pair_masks_alike = !(flags & MADTP_ATTN_PLAN_PAIR_MASKS_DIFFER);
+    AttnResources res;
+    res.hm = resources & MADTP_ATTN_RES_HM; res.opart = resources & MADTP_ATTN_RES_OPART;
+    const AttnPlan pl = attn_plan(p, attn_switches(), res);
+    memcpy(plan, &pl, sizeof(pl));  // (AttnPlan is MADTP_ATTN_PLAN_FIELDS ints in the documented order: attn_plan.h)
+    return 0;
 }
 
 // The launcher behind every attention entry point.  split_req > 0 is the split-plane output request of the f16x3 layer calls
@@ -2256,69 +2194,20 @@ int madtp_i_attention_launch(const void* q, const void* k, const void* v, const 
                              const float* add_mask, const float* mask_qk, int ld_mask_qk, float* colsum_part, float* p0,
                              float* onorm, int B, int H, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, float scale,
                              int io_dtype, int split_req, void* stream, const int32_t* n_dev, int dev_q_only, int kv_block_rows) {
-    if (!q || !k || !v || !out || B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0) return MADTP_E_BADARG;
-    if (mask_qk && (ld_mask_qk < Nk || Nk > 256)) return MADTP_E_SHAPE;  // the <= 256-key kernels carry the [Nq,Nk] mask
-    if (split_req < 0) split_req = 0;
-    if (kv_block_rows && (kv_block_rows < Nk || Nk > 256 || colsum_part)) return MADTP_E_SHAPE;  // (the <= 256-key kernels without scores)
-    if (kv_batch_index && colsum_part) return MADTP_E_BADARG;  // indexed K/V is a cross-attention feature
-    // io_dtype MADTP_F16S: f32 storage, products as three f16 MFMA products of f16-split operands (the f16x3 precision mode)
-    if (io_dtype != MADTP_F32 && io_dtype != MADTP_BF16 && io_dtype != MADTP_F16S && io_dtype != MADTP_F16) return MADTP_E_DTYPE;
-    bool f16s = io_dtype == MADTP_F16S;
-    const bool f16 = io_dtype == MADTP_F16;  // plain f16 operands: the bf16 kernels on the f16 MFMA
-    int split_dim = 0;
-    if (f16s) {
-        f16s = madtp_internal_attn_f16s_enabled();
-        io_dtype = MADTP_F32;
-        split_dim = f16s ? split_req : 0;
-        if (split_req && !f16s) return MADTP_E_BADARG;  // (the caller asks for planes only when the f16s kernels are on)
-    } else if (split_req) {
-        return MADTP_E_BADARG;
-    }
-    if (colsum_part && (!p0 || !onorm || Nq != Nk)) return MADTP_E_BADARG;
-    const int esz = (io_dtype == MADTP_BF16 || f16) ? 2 : 4;
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || (ldq * esz) % 16 || (ldk * esz) % 16 || (ldv * esz) % 16)
-        return MADTP_E_ALIGN;
-    if (Nk > 1024) return MADTP_E_SHAPE;
-    AttnArgs a;
-    a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.out = (char*)out; a.mask = add_mask;
+    AttnProblem p = attn_problem(B, H, Nq, Nk, ldq, ldk, ldv, ldo, io_dtype, split_req);
+    p.ptrs = q && k && v && out;
+    p.scores = colsum_part; p.p0 = p0; p.onorm = onorm;
+    p.mask_qk = mask_qk; p.ld_mask_qk = ld_mask_qk; p.add_mask = add_mask;
+    p.kv_index = kv_batch_index; p.kv_block_rows = kv_block_rows;
+    p.n_dev = n_dev; p.dev_q_only = dev_q_only;
+    p.qkv_aligned = aligned16(q) && aligned16(k) && aligned16(v);
+    p.out_aligned16 = aligned16(out); p.out_aligned8 = !((uintptr_t)out & 7);
+    AttnArgs a = attn_args(q, k, v, out, add_mask, kv_batch_index, B, H, Nq, Nk, ldq, ldk, ldv, ldo, scale);
     a.colsum = colsum_part; a.p0 = p0; a.onorm = onorm;
-    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-    a.nrt = (Nq + 15) / 16;
-    a.scale = scale;
-    a.kvidx = kv_batch_index;
-    a.pair = 0; a.q2 = a.k2 = a.v2 = nullptr; a.out2 = nullptr; a.mask2 = nullptr; a.hm_ws = nullptr; a.hm_tick = nullptr; a.o_part = nullptr;
     a.mask_qk = mask_qk; a.ld_mqk = ld_mask_qk;
     a.n_dev = n_dev; a.dev_q_only = dev_q_only;
-    a.kvb = kv_block_rows ? kv_block_rows : Nk;
-    a.split_dim = split_dim; a.range_flag = split_dim ? madtp_internal_range_flag() : nullptr;
-    hipStream_t s = (hipStream_t)stream;
-    const bool scores = colsum_part != nullptr;
-    if (split_dim) {  // planes: 8-byte stores at f16 offsets
-        if ((ldo % 4) || (split_dim % 4) || ((uintptr_t)out & 7)) return MADTP_E_ALIGN;
-        if (Nk > 256) return scores ? dispatch_large_f16s<true>(a, s) : dispatch_large_f16s<false>(a, s);
-        return scores ? dispatch_nt_f16s<true>(a, s) : dispatch_nt_f16s<false>(a, s);
-    }
-    if (Nk > 256) {  // long sequences (384^2 / 480^2 images): two-pass kernels
-        if (f16s && (ldo * 4) % 16 == 0 && aligned16(out))
-            return scores ? dispatch_large_f16s<true>(a, s) : dispatch_large_f16s<false>(a, s);
-        if (io_dtype == MADTP_F32) return scores ? dispatch_large<float, true>(a, s) : dispatch_large<float, false>(a, s);
-        static const int large_env = env_int("MADTP_ATTN_LARGE_F32", 0);  // 1: bf16 storage on the exact-f32 MFMA kernel (A/B runs)
-        if (f16) return scores ? dispatch_bf16_large<true, true>(a, s) : dispatch_bf16_large<false, true>(a, s);
-        if (large_env) return scores ? dispatch_large<bf16_t, true>(a, s) : dispatch_large<bf16_t, false>(a, s);
-        return scores ? dispatch_bf16_large<true>(a, s) : dispatch_bf16_large<false>(a, s);  // fast mode: bf16 MFMA, LDS-DMA ring
-    }
-    if (f16s && (ldo * 4) % 16 == 0 && aligned16(out))
-        return scores ? dispatch_nt_f16s<true>(a, s) : dispatch_nt_f16s<false>(a, s);
-    if (io_dtype == MADTP_F32) return scores ? dispatch_nt<float, true>(a, s) : dispatch_nt<float, false>(a, s);
-    if ((ldk * 2) % 16 || (ldv * 2) % 16) return MADTP_E_ALIGN;
-    if (scores && Nk <= 32 && !mask_qk && !n_dev) {  // short text sequences: one sample per workgroup, heads spread over the waves
-        if (f16) hipLaunchKernelGGL(attn_bf16_small_kernel<true>, dim3(B), dim3(64 * SMALL_NW), 0, s, a);
-        else hipLaunchKernelGGL(attn_bf16_small_kernel<false>, dim3(B), dim3(64 * SMALL_NW), 0, s, a);
-        MADTP_LAUNCH_CHECK();
-        return 0;
-    }
-    if (f16) return scores ? dispatch_nt_bf16<true, true>(a, s) : dispatch_nt_bf16<false, true>(a, s);
-    return scores ? dispatch_nt_bf16<true>(a, s) : dispatch_nt_bf16<false>(a, s);
+    if (kv_block_rows) a.kvb = kv_block_rows;
+    return attn_run(p, a, (hipStream_t)stream);
 }
 
 // Two attention problems of identical shape (no score side outputs) in one launch when they run on the bf16 kernel for
@@ -2336,33 +2225,27 @@ int madtp_i_attention_pair(const void* q0, const void* q1, const void* k0, const
                            const int32_t* kv_batch_index, void* out0, void* out1, const float* add_mask0, const float* add_mask1, int B,
                            int H, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, float scale, int io_dtype, int split_dim,
                            const int32_t* nq_dev, void* stream) {
-    if (nq_dev && (Nk > 256 || Nq > 256)) return MADTP_E_SHAPE;
-    if (!q0 || !q1 || !k0 || !k1 || !v0 || !v1 || !out0 || !out1 || B <= 0 || H <= 0 || Nq <= 0 || Nk <= 0) return MADTP_E_BADARG;
-    static const int pair_env = env_int("MADTP_ATTN_PAIR", 1);  // 0: always two launches (A/B runs)
-    const bool one = pair_env && (io_dtype == MADTP_BF16 || io_dtype == MADTP_F16) && Nk <= 256 && (!add_mask0) == (!add_mask1) && aligned16(q0) &&
-                     aligned16(q1) && aligned16(k0) && aligned16(k1) && aligned16(v0) && aligned16(v1) && (ldq * 2) % 16 == 0 &&
-                     (ldk * 2) % 16 == 0 && (ldv * 2) % 16 == 0;
-    if (!one) {
-        const int rc = madtp_i_attention_launch(q0, k0, v0, kv_batch_index, out0, add_mask0, nullptr, 0, nullptr, nullptr, nullptr, B, H, Nq, Nk,
-                                                ldq, ldk, ldv, ldo, scale, io_dtype, split_dim, stream, nq_dev, nq_dev ? 1 : 0);
-        if (rc) return rc;
-        return madtp_i_attention_launch(q1, k1, v1, kv_batch_index, out1, add_mask1, nullptr, 0, nullptr, nullptr, nullptr, B, H, Nq, Nk, ldq,
-                                        ldk, ldv, ldo, scale, io_dtype, split_dim, stream, nq_dev, nq_dev ? 1 : 0);
-    }
-    if (split_dim) return MADTP_E_BADARG;  // the one-launch branch (bf16 / f16 storage) writes no planes
-    AttnArgs a;
-    a.q = (const char*)q0; a.k = (const char*)k0; a.v = (const char*)v0; a.out = (char*)out0; a.mask = add_mask0;
+    AttnProblem p = attn_problem(B, H, Nq, Nk, ldq, ldk, ldv, ldo, io_dtype, split_dim);
+    p.pair = true;
+    p.ptrs = q0 && q1 && k0 && k1 && v0 && v1 && out0 && out1;
+    p.add_mask = add_mask0; p.pair_masks_alike = (!add_mask0) == (!add_mask1);
+    p.kv_index = kv_batch_index;
+    p.n_dev = nq_dev; p.dev_q_only = true;
+    p.qkv_aligned = aligned16(q0) && aligned16(k0) && aligned16(v0);
+    p.pair_aligned = aligned16(q1) && aligned16(k1) && aligned16(v1);
+    AttnArgs a = attn_args(q0, k0, v0, out0, add_mask0, kv_batch_index, B, H, Nq, Nk, ldq, ldk, ldv, ldo, scale);
     a.q2 = (const char*)q1; a.k2 = (const char*)k1; a.v2 = (const char*)v1; a.out2 = (char*)out1; a.mask2 = add_mask1;
     a.pair = 1;
-    a.mask_qk = nullptr; a.ld_mqk = 0; a.hm_ws = nullptr; a.hm_tick = nullptr; a.n_dev = nq_dev; a.dev_q_only = 1; a.o_part = nullptr;
-    a.colsum = nullptr; a.p0 = nullptr; a.onorm = nullptr; a.split_dim = 0; a.range_flag = nullptr;
-    a.B = B; a.H = H; a.Nq = Nq; a.Nk = Nk; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-    a.kvb = Nk;
-    a.nrt = (Nq + 15) / 16;
-    a.scale = scale;
-    a.kvidx = kv_batch_index;
-    if (io_dtype == MADTP_F16) return dispatch_nt_bf16<false, true>(a, (hipStream_t)stream);
-    return dispatch_nt_bf16<false>(a, (hipStream_t)stream);
+    a.n_dev = nq_dev; a.dev_q_only = 1;
+    const int rc = attn_run(p, a, (hipStream_t)stream);
+    if (rc != ATTN_PAIR_TWO_LAUNCHES) return rc;
+    for (int i = 0; i < 2; ++i) {
+        const int rc2 = madtp_i_attention_launch(i ? q1 : q0, i ? k1 : k0, i ? v1 : v0, kv_batch_index, i ? out1 : out0, i ? add_mask1 : add_mask0, nullptr,
+                                                 0, nullptr, nullptr, nullptr, B, H, Nq, Nk, ldq, ldk, ldv, ldo, scale, io_dtype, split_dim, stream, nq_dev,
+                                                 nq_dev ? 1 : 0);
+        if (rc2) return rc2;
+    }
+    return 0;
 }
 
 #ifdef MADTP_TS_TIMING

@@ -56,4 +56,4 @@ MADTP_INTERNAL int madtp_i_attention_launch(const void* q, const void* k, const 
                                             float* onorm, int B, int H, int Nq, int Nk, int ldq, int ldk, int ldv, int ldo, float scale,
                                             int io_dtype, int split_dim, void* stream, const int32_t* n_dev = nullptr,
                                             int dev_q_only = 0, int kv_block_rows = 0);
-MADTP_INTERNAL bool madtp_internal_attn_f16s_enabled();  // the f16s attention kernels are on (MADTP_ATTN_F16S != 0)
+MADTP_INTERNAL bool madtp_internal_attn_f16s_enabled();  // the f16s attention kernels are on (attn_plan.h AttnSwitches::f16s)

@@ -26,6 +26,7 @@ _SIGS = {
     "madtp_gemm": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_int, c_int, c_int, c_float, c_float, c_void_p]),
     "madtp_gemm_set_config": (c_int, [c_int]),
     "madtp_gemm_plan": (c_int, [c_int] * 11 + [c_void_p, c_void_p, c_int]),
+    "madtp_attention_plan": (c_int, [c_int] * 14 + [c_void_p, c_int]),
     "madtp_stream_create_cumask": (c_int, [c_void_p, c_void_p, c_int]),
     "madtp_stream_set_sched": (c_int, [c_void_p, c_int, c_float, c_int]),
     "madtp_stream_get_sched": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -342,6 +343,29 @@ def gemm_plan(M, N, K, lda, ldw, ldc, ldr, ab_dtype, c_dtype, splitk=1, flags=0,
     at least len(PLAN_FIELDS) to fill instead (returned as is)."""
     buf = (ctypes.c_int32 * len(PLAN_FIELDS))() if out is None else out
     _check(load().madtp_gemm_plan(M, N, K, lda, ldw, ldc, ldr, ab_dtype, c_dtype, splitk, flags, stream, buf, len(PLAN_FIELDS)), "madtp_gemm_plan")
+    return list(buf) if out is None else out
+
+
+# flags of madtp_attention_plan (include/madtp_hip.h MADTP_ATTN_PLAN_*), its resource bits and the fields it writes
+(ATTN_PLAN_PAIR, ATTN_PLAN_SCORES, ATTN_PLAN_MASK_QK, ATTN_PLAN_ADD_MASK, ATTN_PLAN_KV_INDEX, ATTN_PLAN_N_DEV, ATTN_PLAN_DEV_Q_ONLY,
+ ATTN_PLAN_NULL_PTR, ATTN_PLAN_NO_P0, ATTN_PLAN_NO_ONORM, ATTN_PLAN_QKV_UNALIGNED, ATTN_PLAN_OUT_UNALIGNED16, ATTN_PLAN_OUT_UNALIGNED8,
+ ATTN_PLAN_PAIR_UNALIGNED, ATTN_PLAN_PAIR_MASKS_DIFFER) = (1 << i for i in range(15))
+ATTN_RES_HM, ATTN_RES_OPART = 1, 2
+ATTN_PLAN_FIELDS = ("status", "family", "nt", "storage", "scores", "f16", "hs", "rb", "hv", "gx", "gy", "gz", "block", "lds", "lds_optin", "need_hm",
+                    "need_opart", "split_dim")
+ATTN_FAMILIES = ("attn_kernel", "attn_f16s_kernel", "attn_bf16_kernel", "attn_bf16_small_kernel", "attn_large_kernel", "attn_large_f16s_kernel",
+                 "attn_bf16_large_kernel")
+ATTN_PAIR_TWO_LAUNCHES = 1000  # status: madtp_attention_pair runs this pair as two launches
+
+
+def attention_plan(B, H, Nq, Nk, ldq, ldk, ldv, ldo, io_dtype, ld_mask_qk=0, kv_block_rows=0, split_req=0, flags=0,
+                   resources=ATTN_RES_HM | ATTN_RES_OPART, out=None):
+    """madtp_attention_plan (include/madtp_hip.h): the dispatch decision a madtp_attention* launch of this problem would take - kernel
+    family and instantiation, grid, workgroup size, LDS bytes - as a list of ints in ATTN_PLAN_FIELDS order.  No GPU needed.  `out`:
+    a ctypes int32 array of at least len(ATTN_PLAN_FIELDS) to fill instead (returned as is)."""
+    buf = (ctypes.c_int32 * len(ATTN_PLAN_FIELDS))() if out is None else out
+    _check(load().madtp_attention_plan(B, H, Nq, Nk, ldq, ldk, ldv, ldo, io_dtype, ld_mask_qk, kv_block_rows, split_req, flags, resources, buf,
+                                       len(ATTN_PLAN_FIELDS)), "madtp_attention_plan")
     return list(buf) if out is None else out
 
 

@@ -307,13 +307,16 @@ def _ref_attention(qkv, B, N, H, scale, mask=None):
     return o.transpose(1, 2).reshape(B * N, H * 64), p, colsum, p[:, :, 0, :], o.norm(dim=-1)
 
 
+# Which kernel instantiation each shape of the attention tests below starts is planned and checked on the CPU
+# (tests/test_attn_plan_cpu.py: together they start every instantiation the default environment can reach).
 @pytest.mark.parametrize("B,N,H", [(2, 197, 12), (3, 20, 12), (1, 1 + 16 * 4, 2), (2, 130, 12), (2, 180, 12), (1, 256, 3), (2, 17, 1),
+                                   (1, 33, 2), (1, 100, 2),   # the 4- and 8-tile instantiations
                                    (1, 577, 12), (2, 901, 3), (1, 257, 2), (1, 1024, 1),
-                                   # 641..1024 keys, all heads: the three-sweep order of attn_bf16_large_kernel (round 5; 6 chunks = a
-                                   # second key half of two chunks, 901 = VQA's token count)
-                                   (2, 700, 12), (1, 901, 12),
-                                   # head split (two workgroups per row block, halves merged through the ticket) on many row
-                                   # blocks at once: 16 x 5 / 24 x 2 blocks, and an odd head count (no split)
+                                   # 641..1024 keys, up to 16 heads, bf16: the three-sweep order of attn_bf16_large_kernel (6 chunks = a
+                                   # second key half of two chunks, 901 = VQA's token count); 20 heads: the one-sweep order
+                                   (2, 700, 12), (1, 901, 12), (1, 641, 20),
+                                   # head split, halves merged through the ticket, on many row blocks at once: 16 x 5 blocks (bf16: four
+                                   # workgroups per row block), 24 x 2 blocks (f32: two), and an odd head count (no split)
                                    (16, 320, 12), (24, 96, 12), (4, 300, 3)])
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_self_attention_with_scores(hip, B, N, H, dtype):
@@ -335,21 +338,33 @@ def test_self_attention_with_scores(hip, B, N, H, dtype):
         assert (on.cpu() - rn).abs().max().item() < (1e-4 if dtype == "f32" else 1e-2) * max(1, rn.max().item())
 
 
-@pytest.mark.parametrize("B,L,Nk", [(2, 20, 143), (3, 35, 197), (1, 5, 9), (64, 20, 130), (2, 20, 577), (1, 35, 901)])
-@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("B,L,Nk", [(2, 20, 143), (3, 35, 197), (1, 5, 9), (64, 20, 130), (2, 20, 577), (1, 35, 901),
+                                    (1, 5, 40), (1, 5, 90), (1, 5, 100), (1, 5, 170), (1, 5, 250), (1, 5, 300)])  # the other key capacities
+@pytest.mark.parametrize("dtype", ["f32", "bf16", "f16", "f16x3"])
 def test_cross_attention(hip, B, L, Nk, dtype):
     H = 12
-    td = torch.float32 if dtype == "f32" else torch.bfloat16
+    td = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "f16x3": torch.float32}[dtype]
     q = _rand(B * L, H * 64, seed=21).to(td)
     kv = _rand(B * Nk, 2 * H * 64, seed=22).to(td)
-    kvd = kv.cuda()
-    out, side = hip.attention(q.cuda(), kvd[:, : H * 64], kvd[:, H * 64:], B, H, L, Nk, 0.125)
+    qd, kvd = q.cuda(), kv.cuda()
+    if dtype == "f16":  # (the "f16" mode's 2-byte operands travel in bf16-typed containers)
+        qd, kvd = qd.view(torch.bfloat16), kvd.view(torch.bfloat16)
+    prev = hip.lp_format()
+    hip.set_lp_format(hip.F16 if dtype == "f16" else prev)  # (the element format alone: no precision mode, which has process-wide settings)
+    try:
+        out, side = hip.attention(qd, kvd[:, : H * 64], kvd[:, H * 64:], B, H, L, Nk, 0.125, split=dtype == "f16x3")
+    finally:
+        hip.set_lp_format(prev)
     assert side is None
+    if dtype == "f16":
+        out = out.view(torch.float16)
     qq = q.float().reshape(B, L, H, 64).transpose(1, 2)
     kk, vv = kv.float().reshape(B, Nk, 2, H, 64).permute(2, 0, 3, 1, 4)
     ref = ((qq @ kk.transpose(-1, -2)) * 0.125).softmax(-1) @ vv
     ref = ref.transpose(1, 2).reshape(B * L, H * 64)
-    tol = 3e-5 if dtype == "f32" else 2e-2
+    # f16 operands: the bound of test_self_attention_f16_operands; f16x3: 3x the exact-f32 kernel's, the criterion of
+    # test_attention_f16_split_products
+    tol = {"f32": 3e-5, "f16x3": 9e-5, "f16": 3e-3}.get(dtype, 2e-2)
     assert (out.float().cpu() - ref).abs().max().item() < tol * max(1, ref.abs().max().item())
 
 
@@ -919,7 +934,7 @@ def test_beam_topk(hip, B, nb, V, ld):
 
 
 @pytest.mark.parametrize("B,N,H", [(2, 197, 12), (3, 20, 12), (1, 65, 2), (2, 130, 12), (2, 82, 12), (1, 256, 3), (2, 17, 1),
-                                   (16, 96, 12), (24, 96, 12), (4, 241, 3),
+                                   (16, 96, 12), (24, 96, 12), (4, 241, 3), (1, 33, 2), (1, 100, 2),
                                    (1, 577, 12), (2, 901, 3), (1, 257, 2), (1, 1024, 1)])   # attn_large_f16s_kernel
 def test_attention_f16_split_products(hip, B, N, H):
     """attn_f16s_kernel / attn_large_f16s_kernel (io_dtype MADTP_F16S: f32 storage, QK^T and P.V as three f16 MFMA products of f16-split operands - the
@@ -1007,7 +1022,8 @@ def test_gemm_f16_operands(hip, M, N, K):
         assert (of - exact.float()).abs().mean().item() < 0.25 * (ob - exact.float()).abs().mean().item()
 
 
-@pytest.mark.parametrize("B,N,H", [(2, 197, 12), (3, 20, 12), (2, 130, 12), (1, 577, 12), (16, 320, 12), (1, 901, 12)])
+@pytest.mark.parametrize("B,N,H", [(2, 197, 12), (3, 20, 12), (2, 130, 12), (1, 577, 12), (16, 320, 12), (1, 901, 12),
+                                   (1, 33, 2), (1, 65, 2), (1, 100, 2), (1, 180, 2), (1, 250, 2), (1, 641, 20)])  # the other key capacities
 def test_self_attention_f16_operands(hip, B, N, H):
     from madtp_amd import runtime
     qkv = _rand(B * N, 3 * H * 64, seed=20)
