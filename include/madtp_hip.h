@@ -824,6 +824,24 @@ int madtp_rank_embeds(const float* q, int ldq, const float* keys, int ldk, int n
 int madtp_rank_scores(const float* scores, int ld, int nq, int nk, const int32_t* tgt_ptr, const int32_t* tgt_idx,
                       int32_t* rank_row, int32_t* rank_tgt, void* stream);
 
+/* ---- The optimizer step (ABI 31 - two added entry points, no signature changed; a stale library fails at load on the missing
+ * symbols): optimizer.step() of the training drivers' torch.optim.AdamW (utils.py create_optimizer; csrc/optim.hip)
+ * over every parameter of a step in one launch, in place.  Per element, in f32, in the order of torch's single-tensor AdamW
+ * (torch/optim/adam.py _single_tensor_adam with decoupled_weight_decay):
+ *   p1 = p * decay                       decay = 1 - lr * weight_decay (1 when weight_decay == 0: the product is then exact)
+ *   m' = m + w1 * (g - m)                w1 = 1 - beta1
+ *   v' = v * beta2 + w2 * g * g          w2 = 1 - beta2
+ *   p' = p1 - step_size * (m' / (sqrt(v') / bc2_sqrt + eps))      step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t)
+ * with a correctly rounded division and square root; the caller forms the scalars in double and rounds each once to f32.
+ * table: device int64 [6, n_tensors]: rows 0-3 the p, g, m (exp_avg), v (exp_avg_sq) f32 pointers, row 4 the element counts,
+ * row 5 the first workgroup of each tensor (prefix sum of madtp_adamw_blocks(numel)); n_blocks = the total.  A tensor whose four
+ * pointers are 16-byte aligned moves in 16-byte pieces, any other (a 4-byte aligned view) element by element with the same
+ * values; a zero-element tensor owns no workgroup.  No atomics, fixed grid: identical calls give identical bits.
+ * table == NULL, n_tensors < 1 or n_blocks < 0: MADTP_E_BADARG; n_blocks == 0: nothing is launched, 0 is returned. */
+int madtp_adamw_blocks(int64_t numel);
+int madtp_adamw_step(const int64_t* table, int n_tensors, int n_blocks, float decay, float w1, float beta2, float w2,
+                     float step_size, float bc2_sqrt, float eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,9 @@ _SIGS = {
     "madtp_rank_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
     "madtp_rank_embeds": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 6 + [c_size_t, c_void_p]),
     "madtp_rank_scores": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 5),
+    # the optimizer step (csrc/optim.hip)
+    "madtp_adamw_blocks": (c_int, [ctypes.c_int64]),
+    "madtp_adamw_step": (c_int, [c_void_p, c_int, c_int] + [c_float] * 7 + [c_void_p]),
     "madtp_token_gather_bwd": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p]),
     "madtp_token_score_bwd": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4
                               + [c_int, c_int, c_int, c_void_p]),
@@ -1539,6 +1542,62 @@ class EmaTable:
         """the kernel alone on the current table (timing of tools/retrieval_train_ab.py)"""
         _check(load().madtp_ema_update(_p(self._table), self._n, self._blocks, self._mf[1], self._mf[2], _stream()),
                "madtp_ema_update")
+
+
+# ---- the optimizer step (include/madtp_hip.h madtp_adamw_step; madtp_amd/optim.py) ----------------------------------------------
+ADAMW_PER_BLOCK = 4096  # elements per workgroup of madtp_adamw_step (csrc/optim.hip; checked against madtp_adamw_blocks at load)
+
+
+def adamw_blocks(numel):
+    """madtp_adamw_blocks in Python (the planner of madtp_amd/optim.py runs without the library)"""
+    return 0 if numel <= 0 else (numel + ADAMW_PER_BLOCK - 1) // ADAMW_PER_BLOCK
+
+
+def adamw_first_blocks(numels):
+    """-> (first workgroup of each tensor, total): the prefix sum of adamw_blocks; a zero-element tensor owns no workgroup"""
+    first, nb = [], 0
+    for n in numels:
+        first.append(nb)
+        nb += adamw_blocks(n)
+    return first, nb
+
+
+class AdamWTable:
+    """Device pointer table of madtp_adamw_step for one bucket of (p, g, m, v) f32 tensors.  The tensors are validated when the
+    table is (re)built; each step compares only the 4 n data pointers (a list of ints) to notice gradients that
+    zero_grad(set_to_none=True) let move, or a `.to()` / load_state_dict that assigned new storage.  A rebuild stages the rows in a
+    NEW pinned buffer and uploads it asynchronously on the current stream: no buffer an upload may still be reading is ever written
+    again (torch's pinned-memory allocator keeps a block that a copy in flight uses out of circulation), and no step waits for the
+    device.  `rebuilds` counts the uploads."""
+
+    def __init__(self):
+        self._ptrs, self._table, self._blocks, self._n = None, None, 0, 0
+        self.rebuilds = 0
+
+    def step(self, tensors, scalars):
+        """tensors: [(p, g, m, v)]; scalars: (decay, w1, beta2, w2, step_size, bc2_sqrt, eps) - optim.adamw_scalars"""
+        ptrs = [t.data_ptr() for quad in tensors for t in quad]
+        lib = load()
+        if ptrs != self._ptrs:
+            dev = tensors[0][0].device
+            for quad in tensors:
+                p = quad[0]
+                for t in quad:
+                    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == p.shape and t.device == dev
+                            and t.layout == torch.strided):
+                        raise RuntimeError("adamw_step: parameter, gradient, exp_avg and exp_avg_sq must be contiguous GPU f32 "
+                                           "tensors of one shape on one device (no CPU fallback)")
+            numels = [quad[0].numel() for quad in tensors]
+            first, nb = adamw_first_blocks(numels)
+            if lib.madtp_adamw_blocks(ADAMW_PER_BLOCK) != 1 or lib.madtp_adamw_blocks(ADAMW_PER_BLOCK + 1) != 2:
+                raise RuntimeError("hip.ADAMW_PER_BLOCK disagrees with madtp_adamw_blocks; rebuild")
+            rows = [ptrs[0::4], ptrs[1::4], ptrs[2::4], ptrs[3::4], numels, first]
+            staging = torch.tensor(rows, dtype=torch.int64).pin_memory()
+            self._table = staging.to(dev, non_blocking=True)
+            self._ptrs, self._blocks, self._n = ptrs, nb, len(tensors)
+            self.rebuilds += 1
+        with torch.cuda.device(self._table.device):
+            _check(lib.madtp_adamw_step(_p(self._table), self._n, self._blocks, *scalars, _stream()), "madtp_adamw_step")
 
 
 def itm_negatives(image_feat, text_feat, image_feat_world, text_feat_world, idx, idx_world, temp, u, flag):

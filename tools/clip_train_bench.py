@@ -8,6 +8,8 @@ on the ViT-B/16 checkpoint geometry: B = 16, 224^2, text 77 x 512, vocabulary 49
               composition it replaces, torch.zeros_like(table).index_add_(0, ids, dx) (a 101 MB memset and atomic adds);
   embed:      madtp_clip_embed  vs  (table[ids] + pos).float().contiguous()  (clip/model.py:486-488);
   step:       one forward + backward of CLIP.forward (evaluate=False) in f16x3 and fp32 (no earlier version to compare with).
+              MADTP_TRAIN_OPT=torch | fused | madtp adds the optimizer step of the driver's loop to it (AdamW, lr 1e-6, weight decay
+              0.05: torch's foreach default, torch's fused=True, madtp_amd.optim.AdamW); unset: no optimizer step, as recorded so far.
 The two sides of each pair alternate inside every round (shared machine: a drift hits both); each side's figure is the median over
 the rounds of its per-round median of device-event intervals, reported with the min and max of those per-round medians.  Captions
 are CLIP-shaped: SOT, 6 .. 40 words, EOT, zero padding (synth.synth_clip_tokens), so about 49 of 77 positions share id 0.
@@ -113,11 +115,22 @@ def main():
         images = synth.synth_images(B, size, 0, device=dev)
         idx = torch.arange(B, device=dev)
 
+        which = os.environ.get("MADTP_TRAIN_OPT", "")
+        opt = None
+        if which:
+            from madtp_amd import optim
+            params = [p for p in model.parameters() if p.requires_grad]
+            opt = (optim.AdamW(params, lr=1e-6, weight_decay=0.05) if which == "madtp" else
+                   torch.optim.AdamW(params, lr=1e-6, weight_decay=0.05, **({"fused": True} if which == "fused" else {})))
+            res["step_optimizer"] = which
+
         def step(mode):
             model.zero_grad(set_to_none=True)
             with runtime.precision(mode), runtime.training_f16x3(mode == "f16x3"):
                 ls = model(images, text, 0.4, idx, temperature=4.0)
                 (ls[0] + 0.1 * ls[1] + 0.1 * ls[2]).backward()
+            if opt is not None:
+                opt.step()
 
         r = ab({"f16x3": lambda: step("f16x3"), "fp32": lambda: step("fp32")}, 3, max(3, a.rounds), warm=2)
         res["step_temperature"] = 4.0

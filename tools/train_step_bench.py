@@ -18,8 +18,12 @@ MODE = os.environ.get("MADTP_TRAIN_PRECISION", "fp32")
 model = harness.build_nlvr(224, 0, "cuda")
 DROPOUT = os.environ.get("MADTP_TRAIN_DROPOUT", "0") == "1"  # model.train(): dropout 0.1 / DropPath as the reference's loops run
 # (the reference's create_optimizer builds torch.optim.AdamW with its defaults = the foreach implementation on a GPU;
-#  MADTP_TRAIN_FUSED_ADAM=1: torch's fused=True variant, for the record)
-opt = torch.optim.AdamW(model.parameters(), lr=1e-6, weight_decay=0.05, **({"fused": True} if os.environ.get("MADTP_TRAIN_FUSED_ADAM") == "1" else {}))
+#  MADTP_TRAIN_FUSED_ADAM=1: torch's fused=True variant, for the record; MADTP_TRAIN_OPT=madtp: madtp_amd.optim.AdamW, one launch)
+if os.environ.get("MADTP_TRAIN_OPT", "torch") == "madtp":
+    from madtp_amd import optim  # noqa: E402
+    opt = optim.AdamW(model.parameters(), lr=1e-6, weight_decay=0.05)
+else:
+    opt = torch.optim.AdamW(model.parameters(), lr=1e-6, weight_decay=0.05, **({"fused": True} if os.environ.get("MADTP_TRAIN_FUSED_ADAM") == "1" else {}))
 for B in [int(a) for a in sys.argv[1:]] or [4, 16, 64]:
     images, text, _ = harness.nlvr_inputs(B, 224, 20, 0, "cuda")
     targets = (torch.arange(B) % 2).cuda()
@@ -49,5 +53,5 @@ for B in [int(a) for a in sys.argv[1:]] or [4, 16, 64]:
         torch.cuda.synchronize()
         t_tr = (time.time() - t0) / 3
     model.eval()
-    print(f"B={B:3d} samples ({2 * B} images): inference forward ({MODE} mode) {t_inf * 1e3:8.1f} ms, training step{' (train mode, dropout)' if DROPOUT else ''} {t_tr * 1e3:8.1f} ms "
+    print(f"[{type(opt).__module__}.AdamW{' fused' if opt.param_groups[0]['fused'] else ''}] B={B:3d} samples ({2 * B} images): inference forward ({MODE} mode) {t_inf * 1e3:8.1f} ms, training step{' (train mode, dropout)' if DROPOUT else ''} {t_tr * 1e3:8.1f} ms "
           f"({2 * B / t_tr:7.1f} images/s), peak memory {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB, loss_ori {losses[0]:.4f} -> {losses[-1]:.4f}")
