@@ -23,6 +23,7 @@ import torch
 
 from . import hip
 from .hip import _check, _p, _stream, load
+from .runtime import build_entry, signature
 
 
 def _pad(n, m):
@@ -115,26 +116,19 @@ def _check_mode(what):
 
 
 def _cached(key, tensors, build):
-    """build() memoised per (key, identity and version of the source tensors): padded / concatenated / transposed / split copies of
-    parameters are made once per parameter VERSION (an optimizer step bumps it) instead of in every backward."""
-    from .runtime import update_epoch, param_step_count
-    # (version, per-parameter optimizer step count, process-wide epoch of hand edits: fused optimizers bump no version, runtime.py)
-    ver = tuple((t.data_ptr(), (t._version, param_step_count(t), update_epoch()), tuple(t.shape)) for t in tensors)
+    """build() memoised per (key, runtime.signature of the source tensors): padded / concatenated / transposed / split copies of
+    parameters are made once per parameter VERSION instead of in every backward (previous value for the builder: runtime.reusable)."""
+    sig = signature(tensors)
     hit = _CACHE.get(key)
-    if hit is not None and hit[0] == ver:
-        return hit[1]
-    # (the entry holds its sources alive, so the same addresses and shapes ARE the same parameters at an older version: a builder
-    #  that asks for it gets the previous value - the f16-split scale of a weight is reused across OPTIMIZER STEPS, runtime.SCALE_REUSE:
-    #  every source that changed was changed by a step; a load_state_dict / copy_ / hand edit prepares from scratch)
-    same = (hit is not None and len(hit[0]) == len(ver) and all(a[0] == b[0] and a[2] == b[2] for a, b in zip(hit[0], ver))
-            and all(a[1] == b[1] or (a[1][1] != b[1][1] and a[1][2] == b[1][2]) for a, b in zip(hit[0], ver)))
-    val = build(hit[1] if same else None) if getattr(build, "_takes_prev", False) else build()
+    if hit is not None and hit[0] == sig:
+        return hit[2]
+    hit = build_entry(hit, sig, tensors, build)
     if len(_CACHE) > 4096:
         _CACHE.clear()
     # the entry holds the source tensors: while it lives their storage cannot be recycled for another tensor at the same address
     # (a key of addresses + versions alone would alias a freed model's weights with a new model's)
-    _CACHE[key] = (ver, val, tuple(t.detach() for t in tensors))
-    return val
+    _CACHE[key] = hit + (tuple(t.detach() for t in tensors if t is not None),)
+    return hit[2]
 
 
 def _planes(w32, prev=None):
@@ -234,7 +228,8 @@ def _attention(q, k, v, B, H, Nq, Nk, scale, **kw):
 
 
 def dgrad(dy, weight, residual=None):
-    """dX[M, K] = dY[M, N] @ W[N, K] (nn.Linear weight layout) [+ residual[M, K]: the other branch of a residual connection]."""
+    """dX[M, K] = dY[M, N] @ W[N, K] (nn.Linear weight layout) [+ residual[M, K]: the other branch of a residual connection].
+    weight: the Parameter itself where there is one (the W^T cache's reuse hint reads its step count)."""
     x3 = _x3()
     if x3 and weight.dtype == torch.float16:  # the planes of a fused projection (_cat_wb): its W^T planes ride along
         wtp, N, K = weight._madtp_t, weight._madtp_n, weight.shape[1] // 2
@@ -251,7 +246,7 @@ def dgrad(dy, weight, residual=None):
     # [Kpad, Np]: the GEMM's "weight" with K' = N contiguous - once per parameter version (was: one transpose per backward call)
     if wtp is not None:
         return hip.gemm(hip.split_f16(dy.contiguous()), wtp, None, residual, out_dtype=torch.float32, n=K)
-    wt = _cached(("wt", weight.data_ptr(), Np, x3), [weight], _versioned(lambda: transpose_pad(weight, Np, _pad(K, 128))))
+    wt = _cached(("wt", weight.data_ptr(), Np, x3), [weight], _versioned(lambda: transpose_pad(weight.detach(), Np, _pad(K, 128))))
     if x3:
         return hip.gemm(hip.split_f16(dy.contiguous()), _planes(wt), None, residual, out_dtype=torch.float32, n=K)
     if lp:
@@ -437,19 +432,15 @@ def _pad_w(w):
 
 def _f32_lin(linear):
     """(weight padded to 128 rows, bias) of an nn.Linear for the recomputed forward's GEMM (cached per parameter version)."""
-    b = None if linear.bias is None else linear.bias.detach().contiguous()
-    if _x3_ok(linear.weight):
-        return _x3_weights(("x3w", linear.weight.data_ptr(), tuple(linear.weight.shape)), [linear.weight]).planes, b
-    w = _cached(("pw", linear.weight.data_ptr(), _x3()), [linear.weight], _versioned(lambda: _fresh(_pad_w(linear.weight))))
-    return w, b
+    return _f32_wb(linear.weight, linear.bias)
 
 
 def _f32_wb(w, b):
     """(weight padded to 128 rows, bias) of a Linear given as tensors (cached per parameter version)."""
+    b = None if b is None else b.detach().contiguous()
     if _x3_ok(w):
-        return _x3_weights(("x3w", w.data_ptr(), tuple(w.shape)), [w]).planes, (None if b is None else b.detach().contiguous())
-    wp = _cached(("pw", w.data_ptr(), _x3()), [w], _versioned(lambda: _fresh(_pad_w(w))))
-    return wp, (None if b is None else b.detach().contiguous())
+        return _x3_weights(("x3w", w.data_ptr(), tuple(w.shape)), [w]).planes, b
+    return _cached(("pw", w.data_ptr(), _x3()), [w], _versioned(lambda: _fresh(_pad_w(w)))), b
 
 
 def _fresh(t):
@@ -460,12 +451,10 @@ def _fresh(t):
 def _cat_wb(tag, linears):
     """[w0; w1; ...] and [b0; b1; ...] of Linears that run as one fused projection (cached per parameter version)."""
     ws = [l.weight for l in linears]
-    if all(_x3_ok(x) for x in ws):
-        w = _x3_weights(("x3cat", tag) + tuple(x.data_ptr() for x in ws), ws).planes
-        return w, torch.cat([l.bias.detach() for l in linears], 0).contiguous()
-    w = _cached(("cat", tag, _x3()) + tuple(x.data_ptr() for x in ws), ws, _versioned(lambda: torch.cat([x.detach() for x in ws], 0).contiguous()))
     b = torch.cat([l.bias.detach() for l in linears], 0).contiguous()
-    return w, b
+    if all(_x3_ok(x) for x in ws):
+        return _x3_weights(("x3cat", tag) + tuple(x.data_ptr() for x in ws), ws).planes, b
+    return _cached(("cat", tag, _x3()) + tuple(x.data_ptr() for x in ws), ws, _versioned(lambda: torch.cat([x.detach() for x in ws], 0).contiguous())), b
 
 
 class _BlockParts:
@@ -502,23 +491,14 @@ class _BlockParts:
 def _note_versions(ctx, params):
     """the backward reads the module's CURRENT parameters (W^T planes per parameter version) next to activations of the forward: an
     in-place update between the two (optimizer.step, load_state_dict, an EMA) would pair them wrongly - native autograd raises
-    'modified by an inplace operation' there, so do these Functions"""
-    ctx.param_versions = _versions_of(params)
-
-
-def _versions_of(params):
-    """(process-wide epoch of hand edits, then per parameter: version and optimizer step count).  The step count is per PARAMETER
-    (runtime._on_optimizer_step): a step of another optimizer - a second model, a GAN's other half, a teacher - between this
-    module's forward and backward does not touch it."""
-    from .runtime import update_epoch, param_step_count
-    return (update_epoch(),) + tuple((p._version, param_step_count(p)) if p is not None else -1 for p in params)
+    'modified by an inplace operation' there, so do these Functions (a step of another optimizer over other parameters is none)"""
+    ctx.param_versions = signature(params)
 
 
 def _check_versions(ctx, params, what):
-    now = _versions_of(params)
-    if now != ctx.param_versions:
-        raise RuntimeError(f"{what}: a parameter was modified in place between forward and backward (versions {ctx.param_versions} -> "
-                           f"{now}); back-propagate before the optimizer step / load_state_dict, as native autograd requires")
+    if signature(params) != ctx.param_versions:
+        raise RuntimeError(f"{what}: a parameter was modified in place between forward and backward; back-propagate before the "
+                           "optimizer step / load_state_dict, as native autograd requires")
 
 
 def _second_backward_guard(ctx, what):
@@ -672,10 +652,10 @@ def vit_block_backward(blk, x, token_attn, temperature, k, dy, mask_qk=None, dp_
     drop = getattr(s, "drop", None)
     dy2 = dy.reshape(M2, D).contiguous().float()
     dyb = dropout(dy2, drop[0], drop[1], _site(drop[2], 1), per_sample=N2 * D) if drop is not None else dy2  # the MLP branch's share
-    dg = dgrad(dyb, P.fc2.weight.detach())               # y = y0 + drop_path(g W2^T + b2)
+    dg = dgrad(dyb, P.fc2.weight)                        # y = y0 + drop_path(g W2^T + b2)
     grads[nm["fc2"] + ".weight"], grads[nm["fc2"] + ".bias"] = wgrad(dyb, g, bias=True)
     du = act_bwd(u, dg, P.act)
-    dh2 = dgrad(du, P.fc1.weight.detach())
+    dh2 = dgrad(du, P.fc1.weight)
     grads[nm["fc1"] + ".weight"], grads[nm["fc1"] + ".bias"] = wgrad(du, h2, bias=True)
     dy0, grads[nm["norm2"] + ".weight"], grads[nm["norm2"] + ".bias"] = layernorm_bwd(y02, P.norm2.weight.detach(), dh2, eps2, add=dy2)
     dta = None
@@ -687,10 +667,10 @@ def vit_block_backward(blk, x, token_attn, temperature, k, dy, mask_qk=None, dp_
     else:
         dxa2 = dy0
     dpb = dropout(dxa2.contiguous(), drop[0], drop[1], _site(drop[2], 0), per_sample=N * D) if drop is not None else dxa2
-    dout = dgrad(dpb, P.proj.weight.detach())           # x_attn = x + drop_path(out Wp^T + bp)
+    dout = dgrad(dpb, P.proj.weight)                    # x_attn = x + drop_path(out Wp^T + bp)
     grads[nm["proj"] + ".weight"], grads[nm["proj"] + ".bias"] = wgrad(dpb, out, bias=True)
     dqkv = attention_bwd(qkv, dout, out, B, H, N, scale, dnrm, da, dp0, mask_qk=mask_qk, dp_out=dp_out)
-    dh1 = dgrad(dqkv, P.qkv_w.detach())
+    dh1 = dgrad(dqkv, P.qkv_w)
     if P.qkv_b is not None:
         grads[nm["qkv_w"]], grads[nm["qkv_b"]] = wgrad(dqkv, h1, bias=True)
     else:
@@ -818,7 +798,7 @@ def _cross_branch_bwd(prefix, sm, grads, dcctx, cq, ckv, wckv, y02, enc2, B, H, 
     """Backward of one cross-attention branch; -> (dy0_acc + its contribution to the layer tokens, d encoder tokens [B*Nk, Denc])."""
     D = H * 64
     dcq, dckv = attention_bwd_cross(cq, ckv, dcctx, B, H, L2, Nk, scale, key_mask=key_mask, drop=drop)
-    dy0 = dgrad(dcq, sm.query.weight.detach(), residual=dy0_acc)
+    dy0 = dgrad(dcq, sm.query.weight, residual=dy0_acc)
     grads[prefix + "query.weight"], grads[prefix + "query.bias"] = wgrad(dcq, y02, bias=True)
     denc = dgrad(dckv, wckv)
     gw, gb = wgrad(dckv, enc2, bias=True)
@@ -959,10 +939,10 @@ def med_layer_backward(layer, hidden, mask2d, token_attn, temperature, k, dy, en
     hd = (lambda t, code: dropout(t.contiguous(), ph, drop[2], _site(drop[3], code))) if ph > 0.0 else (lambda t, code: t)
     adrop = (lambda code: (pa, drop[2], _site(drop[3], code))) if pa > 0.0 else (lambda code: None)
     dfb = hd(df0, 5)
-    dgl = dgrad(dfb, layer.output.dense.weight.detach())
+    dgl = dgrad(dfb, layer.output.dense.weight)
     grads["output.dense.weight"], grads["output.dense.bias"] = wgrad(dfb, gl, bias=True)
     du = act_bwd(u, dgl, hip.ACT_GELU)
-    dx2 = dgrad(du, layer.intermediate.dense.weight.detach(), residual=df0)   # f0 = x2 + ffn(x2)
+    dx2 = dgrad(du, layer.intermediate.dense.weight, residual=df0)            # f0 = x2 + ffn(x2)
     grads["intermediate.dense.weight"], grads["intermediate.dense.bias"] = wgrad(du, x2, bias=True)
     denc = None
     if enc is not None:
@@ -972,7 +952,7 @@ def med_layer_backward(layer, hidden, mask2d, token_attn, temperature, k, dy, en
         dcb = hd(dc0, 4)
         if twin:
             if co.merge:
-                dd01 = dgrad(dcb, co.merge_layer.weight.detach())             # [M2, 2D]
+                dd01 = dgrad(dcb, co.merge_layer.weight)                      # [M2, 2D]
                 grads[P + "output.merge_layer.weight"], grads[P + "output.merge_layer.bias"] = wgrad(dcb, d01, bias=True)
                 dds = [dd01[:, :D].contiguous(), dd01[:, D:].contiguous()]
             else:
@@ -982,7 +962,7 @@ def med_layer_backward(layer, hidden, mask2d, token_attn, temperature, k, dy, en
             for i, (sm, dd) in enumerate(zip(sms, dds)):
                 dn = (co.dense0, co.dense1)[i]
                 cq, ckv, cctx, wckv = br[i]
-                dcctx = dgrad(dd, dn.weight.detach())
+                dcctx = dgrad(dd, dn.weight)
                 grads[P + f"output.dense{i}.weight"], grads[P + f"output.dense{i}.bias"] = wgrad(dd, cctx, bias=True)
                 dy0, de = _cross_branch_bwd(P + f"self{i}.", sm, grads, dcctx, cq, ckv, wckv, y02, enc2s[i], B, H, L2, Nk, scale,
                                             ems[i], dy0, drop=adrop(2 + i))
@@ -990,7 +970,7 @@ def med_layer_backward(layer, hidden, mask2d, token_attn, temperature, k, dy, en
             denc = dencs
         else:
             cq, ckv, cctx, wckv = br[0]
-            dcctx = dgrad(dcb, co.dense.weight.detach())
+            dcctx = dgrad(dcb, co.dense.weight)
             grads[P + "output.dense.weight"], grads[P + "output.dense.bias"] = wgrad(dcb, cctx, bias=True)
             dy0, de = _cross_branch_bwd(P + "self.", sms[0], grads, dcctx, cq, ckv, wckv, y02, enc2s[0], B, H, L2, Nk, scale, None, dc0,
                                         drop=adrop(2))
@@ -1008,7 +988,7 @@ def med_layer_backward(layer, hidden, mask2d, token_attn, temperature, k, dy, en
     da0, grads["attention.output.LayerNorm.weight"], grads["attention.output.LayerNorm.bias"] = layernorm_bwd(
         a0, ln1.weight.detach(), dao.contiguous(), ln1.eps)
     dab = hd(da0, 1)
-    dctx = dgrad(dab, so.dense.weight.detach())                               # a0 = hidden + dropout(ctx Wo^T + bo)
+    dctx = dgrad(dab, so.dense.weight)                                        # a0 = hidden + dropout(ctx Wo^T + bo)
     grads["attention.output.dense.weight"], grads["attention.output.dense.bias"] = wgrad(dab, ctx, bias=True)
     dqkv = attention_bwd(qkv, dctx, ctx, B, H, L, scale, dnrm, da, dp0, key_mask=mask2d, mask_qk=causal, drop=adrop(0))
     dh = dgrad(dqkv, wqkv, residual=da0)
@@ -1178,12 +1158,12 @@ class QueryModelFunction(torch.autograd.Function):
             if datt is not None:
                 att_ft_bwd(ta, q, datt.contiguous().float(), ctx.sd_dim, dinner, dq)
             d2 = dinner.view(B * n, K)
-            dq2 = dgrad(d2, sd.detach(), residual=dq.view(B * n, -1))
+            dq2 = dgrad(d2, sd, residual=dq.view(B * n, -1))
             dsd = wgrad(d2, q.reshape(B * n, -1)) if ctx.needs_input_grad[2] else None
             gmap = ()
             if ctx.has_map:
                 gmap = wgrad(dq2, ft.view(B * n, D), bias=True)
-                dq2 = dgrad(dq2, wm.detach())
+                dq2 = dgrad(dq2, wm)
             dx = None
             if ctx.needs_input_grad[1]:
                 dx = torch.zeros_like(x)
@@ -1303,7 +1283,7 @@ class LinearFunction(torch.autograd.Function):
         with torch.no_grad(), _in_mode(ctx.mode):
             dy = dy.contiguous().float()
             du = act_bwd(u, dy, ctx.act) if ctx.act != hip.ACT_NONE else dy
-            dx = dgrad(du, w.detach()) if ctx.needs_input_grad[0] else None
+            dx = dgrad(du, w) if ctx.needs_input_grad[0] else None
             dw = wgrad(du, x) if ctx.needs_input_grad[1] else None
             db = colsum(du) if ctx.has_b else None
         return dx, dw, db, None

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import hip
-from .runtime import autograd_precision as _autograd_precision, EncoderWeights, PreparedCache, param_epoch, own_modules, get_precision, encoder_call_preference, f32_ptr, attn_dtype, compute_dtype, dtype_code, lin_of, require_gpu, as_f32_contig, to_compute
+from .runtime import autograd_precision as _autograd_precision, EncoderWeights, PreparedCache, param_epoch, own_modules, get_precision, encoder_call_preference, f32_ptr, attn_dtype, compute_dtype, dtype_code, lin_of, signature, require_gpu, as_f32_contig, to_compute
 from .utils import Query_model
 
 
@@ -305,7 +305,7 @@ class _BertLayerBase(nn.Module):
         weight / bias holder for lin_of (one-time weight preparation per head-mask tensor version; not a parameter)."""
         store = self.__dict__.setdefault("_hm_store", {})
         wv, bv = sm.value.weight, sm.value.bias
-        sig = (hm.data_ptr(), hm._version, wv.data_ptr(), wv._version, bv.data_ptr(), bv._version)
+        sig = (hm.data_ptr(), hm._version, signature((wv, bv)))
         hit = store.get(id(sm))
         if hit is None or hit[0] != sig:
             rows = hm.repeat_interleave(sm.attention_head_size)

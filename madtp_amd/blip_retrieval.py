@@ -22,7 +22,7 @@ from .bert import BertConfig
 from .blip_nlvr import ENC_TOKEN_ID, create_vit
 from .bert import EncoderKVCache
 from .med import BertModel
-from .runtime import PreparedCache, compute_dtype, lin_of, require_gpu, to_compute
+from .runtime import PreparedCache, compute_dtype, lin_of, note_updated, require_gpu, to_compute
 
 
 def _dist_world():
@@ -150,13 +150,11 @@ class BLIP_Retrieval(nn.Module):
     @torch.no_grad()
     def _momentum_update(self):
         """:293-300 p_m = p_m m + p (1 - m) for every pair in one launch (madtp_ema_update), in place.  The reference assigns new
-        storage; here the storage stays and the update epoch of every momentum parameter is bumped so that the prepared weights of
-        the momentum towers (runtime.PreparedCache) are rebuilt."""
+        storage; here the storage stays and the update is noted, so that the prepared weights of the momentum towers are rebuilt."""
         if self._ema_pairs is None:
             self._ema_pairs = [(pm, p) for p, pm in self.momentum_pairs()]
         self._ema.update(self._ema_pairs, self.momentum)
-        for pm, _ in self._ema_pairs:
-            pm._madtp_steps = getattr(pm, "_madtp_steps", 0) + 1
+        note_updated([pm for pm, _ in self._ema_pairs])
 
     def forward(self, image, caption, alpha, idx, temperature=0, train=True):
         """The training step of blip_retrieval.py:99-282 -> (loss_ita, loss_itm, loss_fdt, loss_fdt_m).  evaluate=False models only.
@@ -330,7 +328,7 @@ class BLIP_Retrieval(nn.Module):
 
     # ---- the small Linears of the evaluation path on the library GEMM ----
     def _linear(self, key, lin, x32):
-        l = lin_of(self._cache, key, [lin])  # (the momentum projections: the cache follows their update epoch)
+        l = lin_of(self._cache, key, [lin])  # (the momentum projections: the cache follows note_updated)
         return hip.gemm(to_compute(x32.contiguous()), l.w, l.b, out_dtype=torch.float32, n=l.n)
 
     def project_image(self, cls_rows):

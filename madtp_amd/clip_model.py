@@ -18,7 +18,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import hip
-from .runtime import autograd_precision as _autograd_precision, PreparedCache, get_precision, f32_ptr, compute_dtype, dtype_code, lin_of, prepare_linear, require_gpu, as_f32_contig, to_compute
+from .runtime import autograd_precision as _autograd_precision, PreparedCache, get_precision, f32_ptr, compute_dtype, dtype_code, lin_of, note_updated, prepare_linear, require_gpu, as_f32_contig, to_compute
 from .utils import DeferredAttFt, Query_model
 
 
@@ -353,12 +353,11 @@ class CLIP(nn.Module):
     @torch.no_grad()
     def _momentum_update(self):
         """:634-643 p_m = p_m m + p (1 - m) for every pair, the two bare parameters included, in one launch (madtp_ema_update),
-        in place; the update epoch of every momentum parameter is bumped so that prepared weights follow (runtime.PreparedCache)."""
+        in place, and noted (runtime.note_updated) so that prepared weights follow."""
         if self._ema_pairs is None:
             self._ema_pairs = [(pm, p) for p, pm in self.momentum_pairs()]
         self._ema.update(self._ema_pairs, self.momentum)
-        for pm, _ in self._ema_pairs:
-            pm._madtp_steps = getattr(pm, "_madtp_steps", 0) + 1
+        note_updated([pm for pm, _ in self._ema_pairs])
 
     @torch.no_grad()
     def _dequeue_and_enqueue(self, image_feat, text_feat, idxs):

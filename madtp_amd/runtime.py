@@ -24,6 +24,7 @@ Precision modes (SURVEY.md section 7 "hard parts"):
 import os
 import threading
 import weakref
+from operator import attrgetter, itemgetter
 
 import torch
 
@@ -161,11 +162,6 @@ class Lin:
         self.w, self.b, self.n, self.log2_scale, self.age = w, b, n, log2_scale, age
 
 
-def param_step_count(p):
-    """how many optimizer steps have updated parameter p in this process (the per-parameter update epoch, see _on_optimizer_step)"""
-    return getattr(p, "_madtp_steps", 0)
-
-
 def _pad_rows(w):
     n = w.shape[0]
     npad = (n + 127) // 128 * 128
@@ -181,9 +177,7 @@ def _pad_rows(w):
 # max|w| 2^s inside the f16 range with the low plane clear of the subnormals, which a slowly moving weight does for many steps: a
 # re-preparation of the SAME cache entry reuses the previous s up to SCALE_REUSE times (two binades of headroom above 2^14; a
 # weight that outgrows them raises the library's range flag - split_f16_weight_kernel / weight_planes_kernel - instead of going
-# wrong silently).  Reuse is for OPTIMIZER STEPS only (small moves): the cache hands the previous value to the builder only when
-# every changed parameter was changed by an optimizer step since (param_step_count); a load_state_dict / copy_ over the same storage
-# (a checkpoint over random-init weights can be orders of magnitude away) takes a fresh scale from max|w|.
+# wrong silently).  Reuse is for OPTIMIZER STEPS only (small moves; the reuse rule under "Parameter changes" below).
 SCALE_REUSE = 64
 
 
@@ -210,8 +204,7 @@ def prepare_linear(weights, biases, dtype, prev=None):
 
 
 class PreparedCache:
-    """Per-module cache of prepared weights, invalidated when a parameter is modified in place, re-assigned,
-    moved, or the precision mode changes (load_state_dict bumps Parameter._version)."""
+    """Per-module cache of prepared weights, invalidated when the precision mode or the parameters' signature() changes."""
 
     MAX_ENTRIES = 32
 
@@ -232,35 +225,22 @@ class PreparedCache:
         self.__init__()
 
     def get(self, key, params, builder):
-        sig = ((get_precision(), _UPDATE_EPOCH[0]),) + tuple((p.data_ptr(), p._version, p.device, getattr(p, "_madtp_steps", 0)) if p is not None else None
-                                                             for p in params)
+        sig = (get_precision(),) + signature(params)
         hit = self._store.get(key)
         if hit is not None and hit[0] == sig:
-            return hit[1]
+            return hit[2]
         with self._lock:  # replicas that share this cache (pipeline.shared_replica) may miss at the same time: one of them builds
-            return self._build(key, sig, builder)
-
-    def _build(self, key, sig, builder):
-        hit = self._store.get(key)
-        if hit is not None and hit[0] == sig:
-            return hit[1]
-        # a builder that takes the entry's previous value (same key and storage, older parameter versions) may reuse parts of it (the
-        # f16-split scale) - only across optimizer steps: every parameter whose version moved has a step count that moved too, and no
-        # hand edit (parameters_updated) happened in between
-        prev = hit[1] if (hit is not None and hit[0][0] == sig[0] and len(hit[0]) == len(sig)
-                          and all((a is None) == (b is None) and (a is None or (a[0] == b[0] and a[2] == b[2] and (a[1] == b[1] or a[3] != b[3])))
-                                  for a, b in zip(hit[0][1:], sig[1:]))
-                          and any(a is not None and a[3] != b[3] for a, b in zip(hit[0][1:], sig[1:]))) else None
-        val = builder(prev) if getattr(builder, "_takes_prev", False) else builder()
-        if self.shared and torch.cuda.is_available():
-            # other host threads will use `val` on THEIR streams: its preparation kernels (casts, splits) must have completed,
-            # not merely been enqueued on this thread's stream (rare: once per weight and precision mode)
-            torch.cuda.current_stream().synchronize()
-        self._store.pop(key, None)
-        self._store[key] = (sig, val)
-        while len(self._store) > self.MAX_ENTRIES:  # bounded: keys may embed id() of caller tensors (a fresh space_dict per call)
-            self._store.pop(next(iter(self._store)))
-        return val
+            hit = self._store.pop(key, None)
+            if hit is None or hit[0] != sig:
+                hit = build_entry(hit, sig, params, builder)
+                if self.shared and torch.cuda.is_available():
+                    # other host threads will use the value on THEIR streams: its preparation kernels (casts, splits) must have
+                    # completed, not merely been enqueued on this thread's stream (rare: once per weight and precision mode)
+                    torch.cuda.current_stream().synchronize()
+            self._store[key] = hit
+            while len(self._store) > self.MAX_ENTRIES:  # bounded: keys may embed id() of caller tensors (a fresh space_dict per call)
+                self._store.pop(next(iter(self._store)))
+            return hit[2]
 
 
 def lin_of(cache, key, linears, dtype=None):
@@ -309,28 +289,79 @@ def param_epoch():
     return _PARAM_EPOCH[0]
 
 
-# In-place parameter UPDATES are normally seen through Parameter._version (every cache signature below carries it) - but not all of
-# them bump it: torch.optim's fused=True implementations (torch._fused_adamw_ and friends) leave _version untouched (checked on this
-# build: a foreach step takes it 0 -> 2, a fused step 0 -> 0), and neither do edits through `.data`.  A stale prepared weight would
-# silently keep multiplying with the old values while LayerNorm parameters (read in place) moved on.  So every optimizer step bumps
-# a step count ON THE PARAMETERS OF THAT OPTIMIZER (a global torch.optim step post-hook walks its param_groups; `_madtp_steps`), which
-# all signatures carry next to the version - scoped per parameter (round 6): a second optimizer, a second model or a frozen inference
-# model in the same process keeps its prepared weights and its forward/backward consistency check.  Code that edits `.data` by hand
-# calls parameters_updated(), which bumps the process-wide epoch (nothing says WHICH parameters moved).
+# ---- Parameter changes: the one place that answers "did this parameter change since I prepared it?" ------------------------------
+# signature(tensors) is what every prepared-weight cache and the forward / backward consistency check compare: the epoch of hand
+# edits, per tensor (data_ptr, device, shape), per tensor Parameter._version - all shared between a Parameter and its detach() alias.
+# The version sees every in-place op and load_state_dict; writers that bump none are made to:
+#   * torch.optim's fused=True steps (a foreach step takes _version 0 -> 2, a fused one 0 -> 0): the global optimizer hooks below bump
+#     what a step left unmoved - of THAT optimizer's parameters: a second optimizer or a frozen model in the process is left alone;
+#   * kernels that write parameters behind torch's back (the EMA of the momentum towers) call note_updated(params);
+#   * edits through `.data` stay invisible (the documented limit) until their author calls parameters_updated(): a process-wide epoch.
+# Reuse rule (reusable): a builder that takes the entry's previous value (the f16-split scale, SCALE_REUSE) gets it only across
+# OPTIMIZER STEPS: all but the versions is unchanged, and every tensor whose version moved has a step count (`_madtp_steps`: optimizer
+# steps and note_updated calls) that moved too.  The count is an attribute of the Parameter OBJECT, which an alias does not share: an
+# entry looked up or built through a plain tensor reads None there and never reuses - a fresh scale, the safe direction.
 _UPDATE_EPOCH = [0]
+_PTR, _VERSION, _IDENT, _FIRST = torch.Tensor.data_ptr, attrgetter("_version"), attrgetter("_madtp_ident"), itemgetter(0)
+_set_versions = torch._C._autograd._unsafe_set_version_counter
+
+
+def signature(tensors):
+    """(epoch, per tensor (data_ptr, device, shape), per tensor _version); None entries stay None.  Device and shape are memoised on the
+    tensor object next to the address they were read at: a held Parameter (EncoderWeights: ~200) costs a data_ptr() and a _version."""
+    try:
+        ids = tuple(map(_IDENT, tensors))
+        if tuple(map(_PTR, tensors)) == tuple(map(_FIRST, ids)):
+            return _UPDATE_EPOCH[0], ids, tuple(map(_VERSION, tensors))
+    except AttributeError:  # a tensor seen for the first time, or a None entry
+        pass
+    for t in tensors:
+        if t is not None:
+            t._madtp_ident = (t.data_ptr(), t.device, t.shape)
+    return (_UPDATE_EPOCH[0], tuple(None if t is None else t._madtp_ident for t in tensors),
+            tuple(None if t is None else t._version for t in tensors))
+
+
+def param_step_count(p):
+    """how many optimizer steps / note_updated calls have updated parameter p in this process"""
+    return getattr(p, "_madtp_steps", 0)
+
+
+def reusable(sig0, steps0, sig1, steps1):
+    """The reuse rule over two (signature [behind a cache's own facts], step counts) stamps of one cache entry."""
+    return sig0[:-1] == sig1[:-1] and all(v0 == v1 or (s0 is not None and s1 is not None and s0 != s1)
+                                          for v0, v1, s0, s1 in zip(sig0[-1], sig1[-1], steps0, steps1))
+
+
+def build_entry(old, sig, tensors, builder):
+    """A cache miss: -> the entry (sig, step counts, value) that replaces `old` (such an entry, or None) under the same key."""
+    steps = tuple(getattr(t, "_madtp_steps", 0) if isinstance(t, torch.nn.Parameter) else None for t in tensors)
+    if not getattr(builder, "_takes_prev", False):
+        return sig, steps, builder()
+    return sig, steps, builder(old[2] if old is not None and reusable(old[0], old[1], sig, steps) else None)
+
+
+def note_updated(params, before=None):
+    """Parameters were written behind torch's back: bump `_version` as its in-place ops do, and the step count (a small move, like an
+    optimizer step).  before: their versions earlier on - what moved since (a foreach step, madtp_amd.optim.AdamW) keeps its own bump."""
+    params = list(params)
+    quiet = params if before is None else [p for p, v in zip(params, before) if p._version == v]
+    _set_versions(quiet, [p._version + 1 for p in quiet])
+    for p in params:
+        p._madtp_steps = getattr(p, "_madtp_steps", 0) + 1
+
+
+def _before_optimizer_step(optimizer, args, kwargs):
+    optimizer._madtp_versions = [p._version for group in optimizer.param_groups for p in group["params"]]
 
 
 def _on_optimizer_step(optimizer, args, kwargs):
-    for group in optimizer.param_groups:
-        for p in group["params"]:
-            p._madtp_steps = getattr(p, "_madtp_steps", 0) + 1
+    note_updated([p for group in optimizer.param_groups for p in group["params"]], optimizer.__dict__.pop("_madtp_versions", ()))
 
 
-try:
-    from torch.optim.optimizer import register_optimizer_step_post_hook as _register_step_hook
-    _register_step_hook(_on_optimizer_step)
-except ImportError:  # (a torch without global optimizer hooks: version counters only)
-    pass
+from torch.optim.optimizer import register_optimizer_step_post_hook, register_optimizer_step_pre_hook  # noqa: E402
+register_optimizer_step_pre_hook(_before_optimizer_step)
+register_optimizer_step_post_hook(_on_optimizer_step)
 
 
 def update_epoch():
@@ -343,15 +374,11 @@ def parameters_updated():
 
 
 class EncoderWeights:
-    """The weight structs of all layers of an encoder for the encoder-level calls (hip.vit_encoder / hip.bert_encoder),
-    revalidated per forward with ONE pass over the flattened parameter list (version counters and data pointers) instead of
-    a PreparedCache lookup per layer - that was ~0.1 ms of host time in front of the first launch of an encoder."""
+    """The weight structs of all layers of an encoder for the encoder-level calls (hip.vit_encoder / hip.bert_encoder), revalidated per
+    forward with ONE signature() of the flattened parameter list instead of a PreparedCache lookup per layer (~0.1 ms of host time)."""
 
     def __init__(self):
         self.flat, self.sig, self.val, self.epoch = None, None, None, -1
-
-    def invalidate(self):
-        self.flat = self.sig = self.val = None
 
     def get(self, layers):
         import ctypes
@@ -361,8 +388,7 @@ class EncoderWeights:
                 l._weights()  # (collects l._madtp_params)
             self.flat = [p for l in layers for p in l.__dict__["_madtp_params"]]
             self.sig = None
-        sig = (get_precision(), _UPDATE_EPOCH[0], tuple([p._version for p in self.flat]), tuple([p.data_ptr() for p in self.flat]),
-               tuple([getattr(p, "_madtp_steps", 0) for p in self.flat]))
+        sig = (get_precision(),) + signature(self.flat)
         if sig != self.sig:
             ws = [l._weights() for l in layers]
             arr = (ctypes.c_void_p * len(ws))(*[ctypes.addressof(w) for w in ws])
@@ -436,12 +462,3 @@ def next_dropout_base():
         b = _DROP_STATE["counter"]
         _DROP_STATE["counter"] = b + 1
         return _DROP_STATE["seed"], b
-
-
-_WARNED_DROPOUT = [False]
-
-
-def warn_no_dropout(module):
-    """kept for callers of earlier rounds: the training forwards now apply the reference's dropout / DropPath in module.train() mode
-    (madtp_amd/backward.py); nothing to warn about."""
-    return None

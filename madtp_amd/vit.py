@@ -223,7 +223,6 @@ class Block(nn.Module):
             # vit.py:88-90 (Grad-CAM): the attention map is saved and its gradient captured.  Here: the map is recomputed on request
             # (get_attention_map(), f32) and the block's backward leaves d loss / d attention-probabilities [B,H,N,N] in
             # get_attn_gradients() - which needs the autograd path, i.e. grad mode on and the fp32 precision mode.
-            from .runtime import get_precision as _gp
             if not (torch.is_grad_enabled() and _autograd_precision()):
                 raise NotImplementedError("register_hook=True captures attention gradients in the block's backward: it needs grad "
                                           "mode on and runtime.precision('fp32')")
@@ -244,7 +243,6 @@ class Block(nn.Module):
             # madtp_amd/backward.py (fp32 precision mode).  An input that asks for a gradient in another mode fails loudly;
             # parameters that merely have requires_grad = True (the nn.Module default) do not force the autograd path there.
             wants = x.requires_grad or (token_attn is not None and token_attn.requires_grad)
-            from .runtime import get_precision
             if wants or (_autograd_precision() and any(p.requires_grad for p in self.parameters())):
                 from .backward import block_forward_with_grad
                 return block_forward_with_grad(self, x, temperature if prune else 0, token_attn)

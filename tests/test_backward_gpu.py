@@ -209,6 +209,57 @@ def test_prepared_weights_follow_fused_optimizers_and_data_edits(hip, mode):
     assert _rel(y2, y1[0]) > 1e-3
 
 
+def _fwd_bwd(blk, mode):
+    x = _rand(2, 50, 768, seed=1).cuda().requires_grad_(True)
+    with _train_mode(mode):
+        (blk(x, temperature=0) * _rand(2, 50, 768, seed=2).cuda()).sum().backward()
+    return x.grad
+
+
+@pytest.mark.parametrize("mode", TRAIN_MODES)
+def test_dgrad_follows_fused_optimizer_steps(hip, mode):
+    """the W^T operands of backward.dgrad (cached per parameter version) after optimizer steps that bump no Parameter._version: two
+    copies of a block with filled caches, one stepped by the foreach AdamW, one by the fused one, back-propagate the same x.grad"""
+    import copy
+    from madtp_amd import vit
+    torch.manual_seed(0)
+    blk_a = vit.Block(768, 12, qkv_bias=True).cuda()
+    blk_b = copy.deepcopy(blk_a)
+    opts = [torch.optim.AdamW(blk_a.parameters(), lr=1e-2), torch.optim.AdamW(blk_b.parameters(), lr=1e-2, fused=True)]
+    g0 = [_fwd_bwd(blk_a, mode), _fwd_bwd(blk_b, mode)]
+    assert torch.equal(g0[0], g0[1])
+    for _ in range(2):
+        for blk, opt in zip((blk_a, blk_b), opts):
+            opt.zero_grad(set_to_none=True)
+            for i, p_ in enumerate(blk.parameters()):  # (the same synthetic gradient for both copies)
+                p_.grad = _rand(*p_.shape, seed=100 + i).cuda()
+            opt.step()
+    g1 = [_fwd_bwd(blk_a, mode), _fwd_bwd(blk_b, mode)]
+    print(f"{mode}: fused vs foreach {_rel(g1[1], g1[0]):.3e}, moved by {_rel(g1[0], g0[0]):.3e}")
+    assert _rel(g1[0], g0[0]) > 1e-2, "the steps changed the block's input gradient"
+    assert _rel(g1[1], g1[0]) < 1e-4, "the fused optimizer's update did not reach the backward's transposed weights"
+
+
+def test_f16x3_weight_planes_survive_forward_backward_alternation(hip):
+    """the forward looks the f16-split planes of a weight up through the Parameter, dgrad through the same key: with nothing updated
+    in between they share one entry (no rebuild per alternation, no SCALE_REUSE age burnt)"""
+    from madtp_amd import backward as bw, vit
+    torch.manual_seed(0)
+    blk = vit.Block(768, 12, qkv_bias=True).cuda()
+    opt = torch.optim.SGD(blk.parameters(), lr=1e-3)
+    _fwd_bwd(blk, "f16x3")
+    opt.step()
+    w = blk.mlp.fc1.weight
+    _fwd_bwd(blk, "f16x3")
+    with _train_mode("f16x3"):
+        o1 = bw._x3_weights(("x3w", w.data_ptr(), tuple(w.shape)), [w])
+    age = o1.age
+    _fwd_bwd(blk, "f16x3")
+    with _train_mode("f16x3"):
+        o2 = bw._x3_weights(("x3w", w.data_ptr(), tuple(w.shape)), [w])
+    assert o2 is o1 and o2.age == age == 1
+
+
 def test_layernorm_bwd(hip):
     from madtp_amd import backward as bw
     rows, dim = 1001, 768

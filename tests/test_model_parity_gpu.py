@@ -1145,6 +1145,42 @@ def test_bert_layer_signature_options_match_reference_fixture(mode, tol, ptol):
                   token_attn=ta[:, :1].clone(), temperature=T)
 
 
+@pytest.mark.parametrize("mode", ["fp32", "bf16"])
+def test_head_masked_layer_follows_fused_optimizer_steps(mode):
+    """the head-masked value projection (bert._scaled_value, a derived weight) after optimizer steps that bump no Parameter._version:
+    two copies of the MED layer of the head_mask case above, text mode, one stepped by the foreach AdamW, one by the fused one"""
+    import copy
+    import os
+    import numpy as np
+    from madtp_amd import build, hip, runtime
+    from tests import grad_case
+    build.build(verbose=False)
+    hip.load()
+    c = grad_case.build_med(np.load(os.path.join(os.path.dirname(__file__), "golden", "medopts_b2.npz")))
+    layers = [grad_case.build_med_layer(c)]
+    layers.append(copy.deepcopy(layers[0]))
+    hid, mask = c["hidden"][:, :20].contiguous().cuda(), c["add_mask"][..., :20].contiguous().cuda()  # B = 2, L = 20
+    hm = torch.linspace(0.5, 1.5, 12).view(1, 12, 1, 1).cuda()
+    rel = lambda a, b: float((a - b).abs().max()) / float(b.abs().max())
+
+    def run():
+        with runtime.precision(mode), torch.no_grad():
+            return [l(hid, mask, hm, None, None, None, False, mode="text", temperature=0)[0] for l in layers]
+
+    y0 = run()
+    assert torch.equal(y0[0], y0[1])
+    opts = [torch.optim.AdamW(layers[0].parameters(), lr=1e-2), torch.optim.AdamW(layers[1].parameters(), lr=1e-2, fused=True)]
+    for _ in range(2):
+        for layer, opt in zip(layers, opts):
+            for i, p_ in enumerate(layer.parameters()):  # (the same synthetic gradient for both copies)
+                p_.grad = torch.randn(p_.shape, generator=torch.Generator().manual_seed(100 + i)).cuda()
+            opt.step()
+    y1 = run()
+    print(f"{mode}: fused vs foreach {rel(y1[1], y1[0]):.3e}, moved by {rel(y1[0], y0[0]):.3e}")
+    assert rel(y1[0], y0[0]) > 1e-2, "the steps changed the layer"
+    assert rel(y1[1], y1[0]) < (1e-4 if mode != "bf16" else 5e-2), "the fused optimizer's update did not reach the head-masked value projection"
+
+
 def test_incremental_decoding_through_the_reference_cache_protocol():
     """BertLMHeadModel.forward(past_key_values=..., use_cache=True) - the protocol transformers' generate drives through
     prepare_inputs_for_generation / _reorder_cache (med.py:1071-1094): feeding a sequence one token at a time against the returned
