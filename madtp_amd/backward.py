@@ -15,15 +15,15 @@ edge); every arithmetic op is a kernel of csrc/backward.hip or madtp_gemm:
 The forward's intermediates are recomputed here from (x, token_attn) with the forward's own kernels and the forward's pruning
 decision k (activation recomputation: nothing but the two inputs is kept alive between forward and backward).
 """
+import contextlib
 import math
-
 import os
 
 import torch
 
-from . import hip
+from . import hip, runtime
 from .hip import _check, _p, _stream, load
-from .runtime import build_entry, signature
+from .runtime import _pad_rows, build_entry, next_dropout_base, signature
 
 
 def _pad(n, m):
@@ -62,43 +62,48 @@ def transpose_split(src, rows_pad, cols_pad, weight, colsum=None):
 #   * a gradient operand dY travels in the ACTIVATION format (P0 + 2^-11 P1: absolute error ~2^-36, so gradients of 1e-6 keep five
 #     digits without a loss scale; the reference trains under autocast + GradScaler, compress_nlvr_dtp.py:46-53, whose scale - if a
 #     caller applies one - simply rides along);
-#   * weights^T travel in the weight format with their per-tensor power-of-two scale (prepared once per parameter version);
-#     wgrad's X^T in the weight format with scale 1 (O(1) activations: ~3e-8 absolute, no host read of max|X|).
+#   * weights and weights^T travel in the weight format with one power-of-two scale per (fused) Linear, prepared once per parameter
+#     version (TrainLin below: the one prepared form of a weight on the training route, in every mode); wgrad's X^T in the weight format with scale 1 (O(1) activations: ~3e-8 absolute, no host read of max|X|).
 _CACHE = {}
 
 
 def _x3():
-    from . import runtime
     return runtime.get_precision() == "f16x3"
 
 
 def _lp():
     """the autocast-style route (runtime.training_amp): the fast modes' 2-byte GEMM operands in the training forward and backward"""
-    from . import runtime
     return runtime.get_precision() in ("bf16", "f16") and runtime.autograd_precision()  # (a fast mode AND the amp opt-in)
 
 
-def _lp_w(w32):
-    """the 2-byte copy (bf16, or f16 of w 2^s tagged with its accumulator scale) of a cached f32 weight / transposed weight, attached
-    to that tensor object (one cast per parameter version and element format)"""
-    hit = getattr(w32, "_madtp_lp_w", None)
-    if hit is None or hit[0] != hip.lp_format():
-        hit = (hip.lp_format(), hip.cast_lp_weight(w32.contiguous()))
-        w32._madtp_lp_w = hit
-    return hit[1]
+def _gemm_mode():
+    """arithmetic of the training route's GEMMs: "f16x3", the amp route's element format "bf16" / "f16", else "fp32" (the exact-f32
+    GEMM: the fp32 mode, and a fast mode without the amp opt-in)"""
+    m = runtime.get_precision()
+    if m in ("fp32", "f16x3"):
+        return m
+    if not runtime.autograd_precision():
+        return "fp32"
+    return "f16" if hip.lp_format() == hip.F16 else "bf16"
+
+
+def _operand(a, dtype):
+    """f32 activation [M, K] -> the A operand of a GEMM whose weight operand has `dtype`: f16-split planes, the 2-byte cast, or a itself"""
+    if dtype == torch.float16:
+        return hip.split_f16(a.contiguous())
+    if dtype == torch.bfloat16:
+        return hip.cast_bf16(a.contiguous())
+    return a
 
 
 def _mode():
-    from . import runtime
     return runtime.get_precision()
 
 
 def _in_mode(mode):
     """context of a backward(): the autograd engine runs it on a worker thread whose thread-local precision mode is the default -
     the forward's mode is recorded on ctx and re-established here"""
-    from . import runtime
     if mode in ("bf16", "f16"):  # a graph built in a fast mode was built under runtime.training_amp(): the backward runs under it too
-        import contextlib
         st = contextlib.ExitStack()
         st.enter_context(runtime.precision(mode))
         st.enter_context(runtime.training_amp())
@@ -107,8 +112,7 @@ def _in_mode(mode):
 
 
 def _check_mode(what):
-    from . import runtime
-    if runtime.get_precision() in ("bf16", "f16") and runtime.autograd_precision():
+    if _lp():
         return  # runtime.training_amp(): approximate gradients on 2-byte operands, asked for
     if runtime.get_precision() not in ("fp32", "f16x3"):
         raise NotImplementedError(f"{what} is built for the fp32-accurate precision modes (runtime.precision('fp32') or 'f16x3'); "
@@ -131,127 +135,135 @@ def _cached(key, tensors, build):
     return hit[2]
 
 
-def _planes(w32, prev=None):
-    """f16-split weight planes of a (padded) f32 weight tensor, attached to it (the tensor itself is a cached object).  prev: the
-    tensor this one replaces in its cache entry - its scale is reused (no host read of max|w|) up to runtime.SCALE_REUSE times."""
-    if w32.dtype == torch.float16:  # already the planes (_x3_weights)
-        return w32
-    pl = getattr(w32, "_madtp_x3_planes", None)
-    if pl is None:
-        from .runtime import SCALE_REUSE
-        s, age = None, 0
-        pp = getattr(prev, "_madtp_x3_planes", None) if prev is not None else None
-        if pp is not None and getattr(prev, "_madtp_x3_age", SCALE_REUSE) < SCALE_REUSE and pp.shape == (w32.shape[0], 2 * w32.shape[1]):
-            s, age = pp._madtp_log2_scale, prev._madtp_x3_age + 1
-        pl = hip.split_f16_weight(w32, log2_scale=s)
-        w32._madtp_x3_planes, w32._madtp_x3_age = pl, age
-    return pl
-
-
-def _versioned(make):
-    """builder for _cached: a (padded / concatenated / transposed) f32 weight copy that, in the f16x3 mode, carries its split planes
-    from the start - prepared with the previous version's scale"""
-    def build(prev=None):
-        t = make()
-        if _x3():
-            _planes(t, prev)
-        return t
-    build._takes_prev = True
-    return build
-
-
-class _X3W:
-    """both operand forms of one (possibly fused) weight in the f16x3 mode: planes [pad128(N), 2K] (forward) and planes_t
-    [pad128(K), 2 pad64(N)] (dgrad), with their common power-of-two scale"""
-    __slots__ = ("planes", "planes_t", "s", "age", "sig")
-
-
-def _x3_weights(key, ws):
-    """f16-split planes of the weight(s) ws (f32 [N_i, K], concatenated along N) and of the transpose, made by ONE kernel per part
-    (madtp_weight_planes) into buffers that are allocated - zero padding included - once per cache entry and rewritten in place for
-    every new parameter version; the scale is the previous version's up to runtime.SCALE_REUSE times (else one host read of max|w|)."""
-    def build(prev=None):
-        from .runtime import SCALE_REUSE
-        Ns, K = tuple(int(w.shape[0]) for w in ws), int(ws[0].shape[1])
-        Nt = sum(Ns)
-        Ntp = _pad(Nt, 64)
-        o = _X3W()
-        o.sig = (Ns, K)
-        if isinstance(prev, _X3W) and prev.sig == o.sig:
-            o.planes, o.planes_t = prev.planes, prev.planes_t
-            o.s, o.age = (prev.s, prev.age + 1) if prev.age < SCALE_REUSE else (None, 0)
-        else:
-            dev = ws[0].device
-            o.planes = torch.zeros((_pad(Nt, 128), 2 * K), device=dev, dtype=torch.float16)
-            o.planes_t = torch.zeros((_pad(K, 128), 2 * Ntp), device=dev, dtype=torch.float16)
-            o.s, o.age = None, 0
-        if o.s is None:
-            amax = float(torch.stack([w.detach().abs().max() for w in ws]).max())
-            o.s = 0
-            if amax > 0 and amax == amax and amax != float("inf"):
-                o.s = max(-100, min(100, 14 - math.ceil(math.log2(amax))))
-        row = 0
-        for w in ws:
-            wd = w.detach()
-            if wd.stride(1) != 1:
-                wd = wd.contiguous()
-            _check(load().madtp_weight_planes(_p(wd), wd.stride(0), int(wd.shape[0]), K, float(2.0 ** o.s), _p(o.planes), row, _p(o.planes_t),
-                                              Ntp, row, _stream()), "madtp_weight_planes")
-            row += int(wd.shape[0])
-        for t in (o.planes, o.planes_t):
-            t._madtp_w_scale, t._madtp_log2_scale = float(2.0 ** -o.s), o.s
-        o.planes._madtp_t, o.planes._madtp_n = o.planes_t, Nt
-        return o
-    build._takes_prev = True
-    return _cached(key, list(ws), build)
-
-
 def _x3_ok(w):
-    """the single-pass weight preparation takes 2-D f32 weights whose K feeds an f16x3 GEMM (K % 64 == 0) and whose N keeps the
-    transposed planes' 4-element groups aligned"""
-    return _x3() and w.dim() == 2 and w.dtype == torch.float32 and w.shape[1] % 64 == 0 and w.shape[0] % 4 == 0
+    """the single-pass weight preparation (madtp_weight_planes) takes 2-D f32 weights whose K feeds an f16x3 GEMM (K % 64 == 0) and
+    whose N keeps the transposed planes' 4-element groups aligned"""
+    return w.dim() == 2 and w.dtype == torch.float32 and w.shape[1] % 64 == 0 and w.shape[0] % 4 == 0
 
 
-def _gemm(a, w, bias=None, n=None, residual=None, out_dtype=torch.float32):
-    """act-free Linear of the recomputed forward: a f32 [M, K] @ w f32 [Npad, K]^T (+ bias, + residual) -> f32 [M, n]."""
-    if _x3() and a.shape[1] % 64 == 0:
-        return hip.gemm(hip.split_f16(a.contiguous()), _planes(w), bias, residual, out_dtype=torch.float32, n=n)
-    if _lp() and a.shape[1] % 64 == 0 and w.dtype == torch.float32:
-        return hip.gemm(hip.cast_bf16(a.contiguous()), _lp_w(w), bias, residual, out_dtype=torch.float32, n=n)
-    return hip.gemm(a, w, bias, residual, out_dtype=torch.float32, n=n)
+class TrainLin:
+    """One (fused) Linear prepared for the training route in one GEMM mode (_gemm_mode): everything the forward, the recomputed
+    forward and dgrad read of the weights [w0; w1; ...] (each [N_i, K]; K zero-padded to kp columns where kp is given).
+      n, k             the true N = sum N_i and K
+      b                the f32 bias (the biases concatenated) or None
+      fwd              the forward GEMM's weight operand [pad128(N), K]: f32, the amp route's 2-byte cast, or f16 planes
+                       [pad128(N), 2K] - and plain f32 in every mode where K % 64 != 0, which only the exact-f32 GEMM takes
+      t                dgrad's operand W^T: f32 [pad128(K), pad32(N)], 2-byte [pad128(K), pad64(N)] or planes [pad128(K), 2 pad64(N)]
+      log2_scale, age  f16x3 mode: the power-of-two scale s both operands share and the parameter versions it has served
+                       (runtime.reuse_scale: the previous version's s up to SCALE_REUSE times, else one host read of max|w|)
+    In the f16x3 mode weights that pass _x3_ok get both operands at once from ONE kernel per part (madtp_weight_planes), into
+    buffers that are allocated - zero padding included - once per cache entry and rewritten in place for every parameter version.
+    Every other operand is made on first use from the padded / transposed f32 copy: a weight whose input needs no gradient never
+    pays for t, one that only dgrad reads (the alignment dictionary) never for fwd."""
+    __slots__ = ("ws", "kp", "mode", "n", "k", "b", "log2_scale", "age", "_fwd", "_t")
+
+    def __init__(self, ws, bs, kp, mode, prev):
+        self.ws, self.kp, self.mode = [w.detach() for w in ws], kp, mode
+        self.n, self.k = sum(int(w.shape[0]) for w in ws), ws[0].numel() // int(ws[0].shape[0])
+        if any(b is None for b in bs):
+            self.b = None
+        else:
+            self.b = (torch.cat([b.detach() for b in bs], 0) if len(bs) > 1 else bs[0].detach()).contiguous()
+        same = prev is not None and [w.shape for w in prev.ws] == [w.shape for w in ws]
+        self.log2_scale, self.age = runtime.reuse_scale(None if prev is None else (prev.log2_scale, prev.age), same)
+        self._fwd = self._t = None
+        if mode == "f16x3" and kp is None and all(_x3_ok(w) for w in ws):
+            self._one_pass(prev if same else None)
+
+    def _one_pass(self, prev):
+        Ntp = _pad(self.n, 64)
+        if prev is not None:
+            self._fwd, self._t = prev._fwd, prev._t
+        else:
+            dev = self.ws[0].device
+            self._fwd = torch.zeros((_pad(self.n, 128), 2 * self.k), device=dev, dtype=torch.float16)
+            self._t = torch.zeros((_pad(self.k, 128), 2 * Ntp), device=dev, dtype=torch.float16)
+        s = self.log2_scale
+        if s is None:
+            s = self.log2_scale = hip.weight_log2_scale(float(torch.stack([w.abs().max() for w in self.ws]).max()))
+        row = 0
+        for w in self.ws:
+            if w.stride(1) != 1:
+                w = w.contiguous()
+            _check(load().madtp_weight_planes(_p(w), w.stride(0), int(w.shape[0]), self.k, float(2.0 ** s), _p(self._fwd), row, _p(self._t),
+                                              Ntp, row, _stream()), "madtp_weight_planes")
+            row += int(w.shape[0])
+        for t in (self._fwd, self._t):
+            t._madtp_w_scale, t._madtp_log2_scale = float(2.0 ** -s), s
+
+    def _make(self, transposed):
+        w = [w if w.dim() == 2 else w.reshape(w.shape[0], -1) for w in self.ws]
+        w = torch.cat(w, 0) if len(w) > 1 else w[0]
+        K = self.kp or self.k
+        if K != self.k:
+            w = torch.nn.functional.pad(w, (0, K - self.k))
+        if transposed:  # N becomes the GEMM's reduction length: slabs of 32 f32 / 64 2-byte elements (zero columns)
+            w32 = transpose_pad(w, _pad(self.n, 32 if self.mode == "fp32" else 64), _pad(K, 128))
+        else:
+            w32 = _pad_rows(w)
+        if self.mode == "fp32" or (K % 64 and not transposed):
+            return w32
+        if self.mode != "f16x3":
+            return hip.cast_lp_weight(w32)
+        pl = hip.split_f16_weight(w32, log2_scale=self.log2_scale)
+        self.log2_scale = pl._madtp_log2_scale
+        return pl
+
+    @property
+    def fwd(self):
+        if self._fwd is None:
+            self._fwd = self._make(False)
+        return self._fwd
+
+    @property
+    def t(self):
+        if self._t is None:
+            self._t = self._make(True)
+        return self._t
+
+
+def train_lin(ws, bs=None, kp=None):
+    """The TrainLin of the weight tensors ws (fused along N) and their biases bs (None: no bias) in the current GEMM mode, prepared
+    once per parameter version.  Pass the Parameters themselves where there are any: the scale reuse reads their step counts."""
+    mode = _gemm_mode()
+    bs = [None] * len(ws) if bs is None else bs
+
+    def build(prev=None):
+        return TrainLin(ws, bs, kp, mode, prev if isinstance(prev, TrainLin) else None)
+    build._takes_prev = True
+    key = ("lin", mode, kp) + tuple((w.data_ptr(), tuple(w.shape)) for w in ws)
+    return _cached(key, list(ws) + [b for b in bs if b is not None], build)
+
+
+def _lin(*linears):
+    """the TrainLin of an nn.Linear, or of several that run as one projection fused along N"""
+    return train_lin([l.weight for l in linears], [l.bias for l in linears])
+
+
+def linear(a, L, residual=None):
+    """act-free Linear of the training / recomputed forward: a f32 [M, K] @ W^T + b (+ residual) -> f32 [M, N]."""
+    w = L.fwd
+    return hip.gemm(_operand(a, w.dtype), w, L.b, residual, out_dtype=torch.float32, n=L.n)
+
+
+def dgrad(dy, L, residual=None):
+    """dX[M, K] = dY[M, N] @ W[N, K] (nn.Linear weight layout) [+ residual[M, K]: the other branch of a residual connection].
+    L: a TrainLin, or the weight itself - the Parameter where there is one - which is prepared here as a bias-free Linear."""
+    if not isinstance(L, TrainLin):
+        L = train_lin([L])
+    wt = L.t
+    Np = wt.shape[1] // 2 if wt.dtype == torch.float16 else wt.shape[1]
+    if Np != L.n:  # zero columns up to the reduction length, for e.g. the 100 dictionary columns
+        dyp = torch.zeros((dy.shape[0], Np), device=dy.device, dtype=torch.float32)
+        dyp[:, :L.n] = dy
+        dy = dyp
+    return hip.gemm(_operand(dy, wt.dtype), wt, None, residual, out_dtype=torch.float32, n=L.k)
 
 
 def _attention(q, k, v, B, H, Nq, Nk, scale, **kw):
     """the recomputed forward's attention: the f16x3 mode's three-product kernels where the forward ran them (and on the amp route:
     q / k / v are f32 there, the three-product kernels are the fast ones for f32 storage)"""
     return hip.attention(q, k, v, B, H, Nq, Nk, scale, split=_x3() or _lp(), **kw)
-
-
-def dgrad(dy, weight, residual=None):
-    """dX[M, K] = dY[M, N] @ W[N, K] (nn.Linear weight layout) [+ residual[M, K]: the other branch of a residual connection].
-    weight: the Parameter itself where there is one (the W^T cache's reuse hint reads its step count)."""
-    x3 = _x3()
-    if x3 and weight.dtype == torch.float16:  # the planes of a fused projection (_cat_wb): its W^T planes ride along
-        wtp, N, K = weight._madtp_t, weight._madtp_n, weight.shape[1] // 2
-    elif x3 and _x3_ok(weight):
-        wtp, (N, K) = _x3_weights(("x3w", weight.data_ptr(), tuple(weight.shape)), [weight]).planes_t, weight.shape
-    else:
-        wtp, (N, K) = None, weight.shape
-    lp = _lp() and not x3
-    Np = _pad(N, 64 if (x3 or lp) else 32)  # the GEMM's reduction length (slabs of 32 f32 / 64 f16): zero columns for e.g. the 100 dictionary columns
-    if Np != N:
-        dyp = torch.zeros((dy.shape[0], Np), device=dy.device, dtype=torch.float32)
-        dyp[:, :N] = dy
-        dy = dyp
-    # [Kpad, Np]: the GEMM's "weight" with K' = N contiguous - once per parameter version (was: one transpose per backward call)
-    if wtp is not None:
-        return hip.gemm(hip.split_f16(dy.contiguous()), wtp, None, residual, out_dtype=torch.float32, n=K)
-    wt = _cached(("wt", weight.data_ptr(), Np, x3), [weight], _versioned(lambda: transpose_pad(weight.detach(), Np, _pad(K, 128))))
-    if x3:
-        return hip.gemm(hip.split_f16(dy.contiguous()), _planes(wt), None, residual, out_dtype=torch.float32, n=K)
-    if lp:
-        return hip.gemm(hip.cast_bf16(dy.contiguous()), _lp_w(wt), None, residual, out_dtype=torch.float32, n=K)
-    return hip.gemm(dy, wt, n=K, out_dtype=torch.float32, residual=residual)
 
 
 def _wgrad_splits(M, N, K):
@@ -268,9 +280,9 @@ def wgrad(dy, x, bias=False):
     pass that transposes dY)."""
     M, N = dy.shape
     K = x.shape[1]
-    x3 = _x3()
-    Mp = _pad(M, 64 if x3 else 32)
-    if x3:  # dY^T in the activation format (tiny values keep their digits), X^T in the weight format at scale 1
+    mode = _gemm_mode()
+    Mp = _pad(M, 32 if mode == "fp32" else 64)
+    if mode == "f16x3":  # dY^T in the activation format (tiny values keep their digits), X^T in the weight format at scale 1
         S = _wgrad_splits(M, N, K)
         Mp = _pad(M, 128 * S) if S else Mp
         a, db = transpose_split(dy, Mp, N, False, colsum=bias)
@@ -286,14 +298,11 @@ def wgrad(dy, x, bias=False):
         else:
             dw = hip.gemm(a, w, n=K, out_dtype=torch.float32)
         return (dw, db) if bias else dw
-    if _lp():
-        Mp = _pad(M, 64)
     dyt = transpose_pad(dy, Mp, N)             # [N, Mp]
     xt = transpose_pad(x, Mp, _pad(K, 128))    # [Kpad, Mp]
-    if _lp():  # amp route: both operands rounded to the mode's 2-byte format (X^T as the "weight" operand at scale 1)
-        dw = hip.gemm(hip.cast_bf16(dyt), hip.cast_bf16(xt), n=K, out_dtype=torch.float32)
-    else:
-        dw = hip.gemm(dyt, xt, n=K, out_dtype=torch.float32)
+    # amp route: both operands rounded to the mode's 2-byte format (X^T as the "weight" operand at scale 1)
+    dt = torch.float32 if mode == "fp32" else torch.bfloat16
+    dw = hip.gemm(_operand(dyt, dt), _operand(xt, dt), n=K, out_dtype=torch.float32)
     return (dw, colsum(dy)) if bias else dw
 
 
@@ -419,44 +428,6 @@ def attention_bwd_cross(q, kv, dout, B, H, Nq, Nk, scale, key_mask=None, drop=No
     return dq, dkv
 
 
-def _pad_w(w):
-    w = w.detach()
-    n = w.shape[0]
-    npad = _pad(n, 128)
-    if npad != n:
-        wp = torch.zeros((npad, w.shape[1]), device=w.device, dtype=torch.float32)
-        wp[:n] = w
-        w = wp
-    return w.contiguous()
-
-
-def _f32_lin(linear):
-    """(weight padded to 128 rows, bias) of an nn.Linear for the recomputed forward's GEMM (cached per parameter version)."""
-    return _f32_wb(linear.weight, linear.bias)
-
-
-def _f32_wb(w, b):
-    """(weight padded to 128 rows, bias) of a Linear given as tensors (cached per parameter version)."""
-    b = None if b is None else b.detach().contiguous()
-    if _x3_ok(w):
-        return _x3_weights(("x3w", w.data_ptr(), tuple(w.shape)), [w]).planes, b
-    return _cached(("pw", w.data_ptr(), _x3()), [w], _versioned(lambda: _fresh(_pad_w(w)))), b
-
-
-def _fresh(t):
-    """a tensor OBJECT of the cache's own (attributes such as the split planes hang on it; never the parameter's storage view)"""
-    return t.detach().view(t.shape) if t.requires_grad else t.view(t.shape)
-
-
-def _cat_wb(tag, linears):
-    """[w0; w1; ...] and [b0; b1; ...] of Linears that run as one fused projection (cached per parameter version)."""
-    ws = [l.weight for l in linears]
-    b = torch.cat([l.bias.detach() for l in linears], 0).contiguous()
-    if all(_x3_ok(x) for x in ws):
-        return _x3_weights(("x3cat", tag) + tuple(x.data_ptr() for x in ws), ws).planes, b
-    return _cached(("cat", tag, _x3()) + tuple(x.data_ptr() for x in ws), ws, _versioned(lambda: torch.cat([x.detach() for x in ws], 0).contiguous())), b
-
-
 class _BlockParts:
     """The modules / tensors of a pruned ViT block under one set of names: BLIP's Block (models/vit.py:106-207) and CLIP's
     ResidualAttentionBlock (clip/model.py:174-261: fused in_proj, QuickGELU, LayerNorm eps 1e-5) run the same layer call."""
@@ -482,6 +453,10 @@ class _BlockParts:
         return (n["norm1"] + ".weight", n["norm1"] + ".bias", n["qkv_w"], n["qkv_b"], n["proj"] + ".weight", n["proj"] + ".bias",
                 n["norm2"] + ".weight", n["norm2"] + ".bias", n["fc1"] + ".weight", n["fc1"] + ".bias", n["fc2"] + ".weight",
                 n["fc2"] + ".bias")
+
+    def qkv(self):
+        """the TrainLin of the fused q/k/v projection"""
+        return train_lin([self.qkv_w], [self.qkv_b])
 
     def params(self):
         return [self.norm1.weight, self.norm1.bias, self.qkv_w, self.qkv_b, self.proj.weight, self.proj.bias, self.norm2.weight,
@@ -546,7 +521,6 @@ def _block_drop(blk):
     p = float(getattr(blk, "drop_path_rate", 0.0) or 0.0)
     if not blk.training or p <= 0.0:
         return None
-    from .runtime import next_dropout_base
     seed, base = next_dropout_base()
     return (p, seed, base)
 
@@ -559,7 +533,6 @@ def _layer_drop(layer):
     pa = float(layer.attention.self.dropout.p)
     if ph <= 0.0 and pa <= 0.0:
         return None
-    from .runtime import next_dropout_base
     seed, base = next_dropout_base()
     return (ph, pa, seed, base)
 
@@ -581,16 +554,14 @@ def _vit_block_fwd(blk, x, token_attn, temperature, k, mask_qk=None, max_keep=0,
     eps1, eps2 = P.norm1.eps, P.norm2.eps
     x2 = x.reshape(M, D)
     h1, _ = hip.layernorm(x2, P.norm1.weight.detach(), P.norm1.bias.detach(), eps1)
-    wq, bq = _f32_wb(P.qkv_w, P.qkv_b)
-    wp, bp = _f32_lin(P.proj)
-    w1, b1 = _f32_lin(P.fc1)
-    qkv = _gemm(h1, wq, bq, n=3 * D, out_dtype=torch.float32)
+    wq, wp, w1 = P.qkv(), _lin(P.proj), _lin(P.fc1)
+    qkv = linear(h1, wq)
     prune = temperature > 0 if k is None else k > 0
     out, side = _attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B, H, N, N, scale, scores=prune, mask_qk=mask_qk)
     if drop is not None:  # x + drop_path(attn(norm1(x))), vit.py:186: one draw per sample
-        x_attn = dropout(_gemm(out, wp, bp, n=D, out_dtype=torch.float32), drop[0], drop[1], _site(drop[2], 0), residual=x2, per_sample=N * D)
+        x_attn = dropout(linear(out, wp), drop[0], drop[1], _site(drop[2], 0), residual=x2, per_sample=N * D)
     else:
-        x_attn = _gemm(out, wp, bp, residual=x2, n=D, out_dtype=torch.float32)
+        x_attn = linear(out, wp, residual=x2)
     score = dst_pos = merge_w = info = None
     if prune and k is None:
         score, thr, count, kk = hip.token_score_sync(side, token_attn, temperature, B, H, N)
@@ -609,7 +580,7 @@ def _vit_block_fwd(blk, x, token_attn, temperature, k, mask_qk=None, max_keep=0,
     N2 = y0.shape[1]
     y02 = y0.reshape(B * N2, D)
     h2, _ = hip.layernorm(y02, P.norm2.weight.detach(), P.norm2.bias.detach(), eps2)
-    u = _gemm(h2, w1, b1, n=P.fc1.weight.shape[0], out_dtype=torch.float32)
+    u = linear(h2, w1)
     g = act_fwd(u, P.act)
     return _Saved(k=k, info=info, h1=h1, qkv=qkv, out=out, side=side, x_attn=x_attn, score=score, dst_pos=dst_pos, merge_w=merge_w,
                   y02=y02, h2=h2, u=u, g=g, drop=drop)
@@ -621,12 +592,12 @@ def vit_block_forward_saved(blk, x, token_attn, temperature, max_keep=0, mask_qk
     B, _, D = x.shape
     drop = _block_drop(blk)
     s = _vit_block_fwd(blk, x, token_attn, temperature, None, mask_qk=mask_qk, max_keep=max_keep, drop=drop)
-    w2, b2 = _f32_lin(P.fc2)
+    w2 = _lin(P.fc2)
     if drop is not None:  # x + drop_path(mlp(norm2(x))), vit.py:205
-        y = dropout(_gemm(s.g, w2, b2, n=D, out_dtype=torch.float32), drop[0], drop[1], _site(drop[2], 1), residual=s.y02,
+        y = dropout(linear(s.g, w2), drop[0], drop[1], _site(drop[2], 1), residual=s.y02,
                     per_sample=(s.y02.shape[0] // B) * D)
     else:
-        y = _gemm(s.g, w2, b2, residual=s.y02, n=D, out_dtype=torch.float32)
+        y = linear(s.g, w2, residual=s.y02)
     return y.view(B, -1, D), s.info, s
 
 
@@ -652,10 +623,10 @@ def vit_block_backward(blk, x, token_attn, temperature, k, dy, mask_qk=None, dp_
     drop = getattr(s, "drop", None)
     dy2 = dy.reshape(M2, D).contiguous().float()
     dyb = dropout(dy2, drop[0], drop[1], _site(drop[2], 1), per_sample=N2 * D) if drop is not None else dy2  # the MLP branch's share
-    dg = dgrad(dyb, P.fc2.weight)                        # y = y0 + drop_path(g W2^T + b2)
+    dg = dgrad(dyb, _lin(P.fc2))                        # y = y0 + drop_path(g W2^T + b2)
     grads[nm["fc2"] + ".weight"], grads[nm["fc2"] + ".bias"] = wgrad(dyb, g, bias=True)
     du = act_bwd(u, dg, P.act)
-    dh2 = dgrad(du, P.fc1.weight)
+    dh2 = dgrad(du, _lin(P.fc1))
     grads[nm["fc1"] + ".weight"], grads[nm["fc1"] + ".bias"] = wgrad(du, h2, bias=True)
     dy0, grads[nm["norm2"] + ".weight"], grads[nm["norm2"] + ".bias"] = layernorm_bwd(y02, P.norm2.weight.detach(), dh2, eps2, add=dy2)
     dta = None
@@ -667,10 +638,10 @@ def vit_block_backward(blk, x, token_attn, temperature, k, dy, mask_qk=None, dp_
     else:
         dxa2 = dy0
     dpb = dropout(dxa2.contiguous(), drop[0], drop[1], _site(drop[2], 0), per_sample=N * D) if drop is not None else dxa2
-    dout = dgrad(dpb, P.proj.weight)                    # x_attn = x + drop_path(out Wp^T + bp)
+    dout = dgrad(dpb, _lin(P.proj))                    # x_attn = x + drop_path(out Wp^T + bp)
     grads[nm["proj"] + ".weight"], grads[nm["proj"] + ".bias"] = wgrad(dpb, out, bias=True)
     dqkv = attention_bwd(qkv, dout, out, B, H, N, scale, dnrm, da, dp0, mask_qk=mask_qk, dp_out=dp_out)
-    dh1 = dgrad(dqkv, P.qkv_w)
+    dh1 = dgrad(dqkv, P.qkv())
     if P.qkv_b is not None:
         grads[nm["qkv_w"]], grads[nm["qkv_b"]] = wgrad(dqkv, h1, bias=True)
     else:
@@ -780,27 +751,26 @@ def _med_params_of(layer, cross):
 
 
 def _cross_branch_fwd(sm, y02, enc2, B, H, L2, Nk, scale, key_mask, drop=None):
-    """One cross-attention branch (BertSelfAttention with encoder_hidden_states): -> (cq, ckv, cctx, wckv).  drop: (p, seed, site) of
+    """One cross-attention branch (BertSelfAttention with encoder_hidden_states): -> (cq, ckv, cctx).  drop: (p, seed, site) of
     the attention_probs dropout or None."""
     D = H * 64
-    wcq, bcq = _f32_lin(sm.query)
-    wckv, bckv = _cat_wb("ckv", [sm.key, sm.value])  # [2D, Denc]
-    cq = _gemm(y02, wcq, bcq, n=D, out_dtype=torch.float32)
-    ckv = _gemm(enc2, wckv, bckv, n=2 * D, out_dtype=torch.float32)
+    wcq, wckv = _lin(sm.query), _lin(sm.key, sm.value)  # wckv: [2D, Denc]
+    cq = linear(y02, wcq)
+    ckv = linear(enc2, wckv)
     if drop is not None:
         cctx, _ = attention_train(cq, ckv[:, :D], ckv[:, D:], B, H, L2, Nk, scale, drop, key_mask=key_mask)
     else:
         cctx, _ = _attention(cq, ckv[:, :D], ckv[:, D:], B, H, L2, Nk, scale, add_mask=key_mask)
-    return cq, ckv, cctx, wckv
+    return cq, ckv, cctx
 
 
-def _cross_branch_bwd(prefix, sm, grads, dcctx, cq, ckv, wckv, y02, enc2, B, H, L2, Nk, scale, key_mask, dy0_acc, drop=None):
+def _cross_branch_bwd(prefix, sm, grads, dcctx, cq, ckv, y02, enc2, B, H, L2, Nk, scale, key_mask, dy0_acc, drop=None):
     """Backward of one cross-attention branch; -> (dy0_acc + its contribution to the layer tokens, d encoder tokens [B*Nk, Denc])."""
     D = H * 64
     dcq, dckv = attention_bwd_cross(cq, ckv, dcctx, B, H, L2, Nk, scale, key_mask=key_mask, drop=drop)
-    dy0 = dgrad(dcq, sm.query.weight, residual=dy0_acc)
+    dy0 = dgrad(dcq, _lin(sm.query), residual=dy0_acc)
     grads[prefix + "query.weight"], grads[prefix + "query.bias"] = wgrad(dcq, y02, bias=True)
-    denc = dgrad(dckv, wckv)
+    denc = dgrad(dckv, _lin(sm.key, sm.value))
     gw, gb = wgrad(dckv, enc2, bias=True)
     for i, nm in enumerate(("key", "value")):
         grads[prefix + nm + ".weight"] = gw[i * D:(i + 1) * D]
@@ -818,11 +788,9 @@ def _med_layer_fwd(layer, hidden, mask2d, token_attn, temperature, k, enc=None, 
     M = B * L
     h2 = hidden.reshape(M, D)
     twin = isinstance(enc, (list, tuple))
-    wqkv, bqkv = _cat_wb("qkv", [sa.query, sa.key, sa.value])  # [3D, D]
-    wo, bo = _f32_lin(so.dense)
-    wi, bi = _f32_lin(layer.intermediate.dense)
-    wout, bout = _f32_lin(layer.output.dense)
-    qkv = _gemm(h2, wqkv, bqkv, n=3 * D, out_dtype=torch.float32)
+    wqkv = _lin(sa.query, sa.key, sa.value)  # [3D, D]
+    wo, wi, wout = _lin(so.dense), _lin(layer.intermediate.dense), _lin(layer.output.dense)
+    qkv = linear(h2, wqkv)
     prune = temperature > 0 if k is None else k > 0
     # drop = (p_hidden, p_attn, seed, base): the layer's dropouts in .train() mode (med.py:55,111,244,323); sites: 0 self-attention
     # probabilities, 1 self-output, 2 / 3 cross-attention probabilities (branch 0 / 1), 4 cross-output, 5 FFN output
@@ -836,9 +804,9 @@ def _med_layer_fwd(layer, hidden, mask2d, token_attn, temperature, k, enc=None, 
         ctx, side = _attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B, H, L, L, scale, add_mask=mask2d, scores=prune,
                                mask_qk=causal)   # causal [L,L]: the decoder's mask (med.py:752-786), never together with pruning
     if ph > 0.0:
-        a0 = hdrop(_gemm(ctx, wo, bo, n=D, out_dtype=torch.float32), h2, 1)   # LayerNorm(dropout(dense(ctx)) + input), med.py:246-250
+        a0 = hdrop(linear(ctx, wo), h2, 1)   # LayerNorm(dropout(dense(ctx)) + input), med.py:246-250
     else:
-        a0 = _gemm(ctx, wo, bo, residual=h2, n=D, out_dtype=torch.float32)
+        a0 = linear(ctx, wo, residual=h2)
     ao, _ = hip.layernorm(a0, so.LayerNorm.weight.detach(), so.LayerNorm.bias.detach(), so.LayerNorm.eps)
     score = dst_pos = merge_w = info = mask_out = None
     if prune and k is None:
@@ -872,30 +840,29 @@ def _med_layer_fwd(layer, hidden, mask2d, token_attn, temperature, k, enc=None, 
         enc2s = [e.reshape(B * Nk, De).contiguous().float() for e in encs]
         br = [_cross_branch_fwd(sm, y02, e2, B, H, L2, Nk, scale, em, drop=adrop(2 + i)) for i, (sm, e2, em) in enumerate(zip(sms, enc2s, ems))]
         if twin:
-            w0, b0 = _f32_lin(co.dense0)
-            w1, b1 = _f32_lin(co.dense1)
-            d0 = _gemm(br[0][2], w0, b0, n=D, out_dtype=torch.float32)
-            d1 = _gemm(br[1][2], w1, b1, n=D, out_dtype=torch.float32)
+            w0, w1 = _lin(co.dense0), _lin(co.dense1)
+            d0 = linear(br[0][2], w0)
+            d1 = linear(br[1][2], w1)
             if co.merge:
                 d01 = torch.cat([d0, d1], 1).contiguous()  # (a copy: the operand layout of merge_layer)
-                wm, bm = _f32_lin(co.merge_layer)
-                c0 = (hdrop(_gemm(d01, wm, bm, n=D, out_dtype=torch.float32), y02, 4) if ph > 0.0   # nlvr_encoder.py:259-271
-                      else _gemm(d01, wm, bm, residual=y02, n=D, out_dtype=torch.float32))
+                wm = _lin(co.merge_layer)
+                c0 = (hdrop(linear(d01, wm), y02, 4) if ph > 0.0   # nlvr_encoder.py:259-271
+                      else linear(d01, wm, residual=y02))
             else:
                 c0 = hdrop(((d0 + d1) * 0.5).contiguous(), y02, 4) if ph > 0.0 else (d0 + d1) * 0.5 + y02
         else:
-            wcd, bcd = _f32_lin(co.dense)
-            c0 = (hdrop(_gemm(br[0][2], wcd, bcd, n=D, out_dtype=torch.float32), y02, 4) if ph > 0.0
-                  else _gemm(br[0][2], wcd, bcd, residual=y02, n=D, out_dtype=torch.float32))
+            wcd = _lin(co.dense)
+            c0 = (hdrop(linear(br[0][2], wcd), y02, 4) if ph > 0.0
+                  else linear(br[0][2], wcd, residual=y02))
         x2, _ = hip.layernorm(c0, co.LayerNorm.weight.detach(), co.LayerNorm.bias.detach(), co.LayerNorm.eps)
     else:
         x2 = y02
     F = layer.intermediate.dense.weight.shape[0]
-    u = _gemm(x2, wi, bi, n=F, out_dtype=torch.float32)
+    u = linear(x2, wi)
     gl = act_fwd(u, hip.ACT_GELU)
-    f0 = (hdrop(_gemm(gl, wout, bout, n=D, out_dtype=torch.float32), x2, 5) if ph > 0.0                # med.py:326-328
-          else _gemm(gl, wout, bout, residual=x2, n=D, out_dtype=torch.float32))
-    return _Saved(drop=drop, k=k, info=info, mask_out=mask_out, wqkv=wqkv, qkv=qkv, ctx=ctx, side=side, a0=a0, ao=ao, score=score, dst_pos=dst_pos,
+    f0 = (hdrop(linear(gl, wout), x2, 5) if ph > 0.0                # med.py:326-328
+          else linear(gl, wout, residual=x2))
+    return _Saved(drop=drop, k=k, info=info, mask_out=mask_out, qkv=qkv, ctx=ctx, side=side, a0=a0, ao=ao, score=score, dst_pos=dst_pos,
                   merge_w=merge_w, y02=y02, br=br, enc2s=enc2s, sms=sms, ems=ems, Nk=Nk, De=De, c0=c0, d01=d01, x2=x2, u=u, gl=gl, f0=f0)
 
 
@@ -922,7 +889,7 @@ def med_layer_backward(layer, hidden, mask2d, token_attn, temperature, k, dy, en
     h2 = hidden.reshape(M, D)
     twin = isinstance(enc, (list, tuple))
     s = saved if saved is not None else _med_layer_fwd(layer, hidden, mask2d, token_attn, temperature, k, enc, enc_masks, causal)
-    wqkv, qkv, ctx, side, a0, ao, score, dst_pos, merge_w = s.wqkv, s.qkv, s.ctx, s.side, s.a0, s.ao, s.score, s.dst_pos, s.merge_w
+    qkv, ctx, side, a0, ao, score, dst_pos, merge_w = s.qkv, s.ctx, s.side, s.a0, s.ao, s.score, s.dst_pos, s.merge_w
     y02, br, enc2s, sms, ems, Nk, De, c0, d01, x2, u, gl, f0 = s.y02, s.br, s.enc2s, s.sms, s.ems, s.Nk, s.De, s.c0, s.d01, s.x2, s.u, s.gl, s.f0
     M2 = y02.shape[0]
     L2 = M2 // B
@@ -939,10 +906,10 @@ def med_layer_backward(layer, hidden, mask2d, token_attn, temperature, k, dy, en
     hd = (lambda t, code: dropout(t.contiguous(), ph, drop[2], _site(drop[3], code))) if ph > 0.0 else (lambda t, code: t)
     adrop = (lambda code: (pa, drop[2], _site(drop[3], code))) if pa > 0.0 else (lambda code: None)
     dfb = hd(df0, 5)
-    dgl = dgrad(dfb, layer.output.dense.weight)
+    dgl = dgrad(dfb, _lin(layer.output.dense))
     grads["output.dense.weight"], grads["output.dense.bias"] = wgrad(dfb, gl, bias=True)
     du = act_bwd(u, dgl, hip.ACT_GELU)
-    dx2 = dgrad(du, layer.intermediate.dense.weight, residual=df0)            # f0 = x2 + ffn(x2)
+    dx2 = dgrad(du, _lin(layer.intermediate.dense), residual=df0)            # f0 = x2 + ffn(x2)
     grads["intermediate.dense.weight"], grads["intermediate.dense.bias"] = wgrad(du, x2, bias=True)
     denc = None
     if enc is not None:
@@ -952,7 +919,7 @@ def med_layer_backward(layer, hidden, mask2d, token_attn, temperature, k, dy, en
         dcb = hd(dc0, 4)
         if twin:
             if co.merge:
-                dd01 = dgrad(dcb, co.merge_layer.weight)                      # [M2, 2D]
+                dd01 = dgrad(dcb, _lin(co.merge_layer))                      # [M2, 2D]
                 grads[P + "output.merge_layer.weight"], grads[P + "output.merge_layer.bias"] = wgrad(dcb, d01, bias=True)
                 dds = [dd01[:, :D].contiguous(), dd01[:, D:].contiguous()]
             else:
@@ -961,18 +928,18 @@ def med_layer_backward(layer, hidden, mask2d, token_attn, temperature, k, dy, en
             dy0, dencs = dc0, []
             for i, (sm, dd) in enumerate(zip(sms, dds)):
                 dn = (co.dense0, co.dense1)[i]
-                cq, ckv, cctx, wckv = br[i]
-                dcctx = dgrad(dd, dn.weight)
+                cq, ckv, cctx = br[i]
+                dcctx = dgrad(dd, _lin(dn))
                 grads[P + f"output.dense{i}.weight"], grads[P + f"output.dense{i}.bias"] = wgrad(dd, cctx, bias=True)
-                dy0, de = _cross_branch_bwd(P + f"self{i}.", sm, grads, dcctx, cq, ckv, wckv, y02, enc2s[i], B, H, L2, Nk, scale,
+                dy0, de = _cross_branch_bwd(P + f"self{i}.", sm, grads, dcctx, cq, ckv, y02, enc2s[i], B, H, L2, Nk, scale,
                                             ems[i], dy0, drop=adrop(2 + i))
                 dencs.append(de.view(B, Nk, De))
             denc = dencs
         else:
-            cq, ckv, cctx, wckv = br[0]
-            dcctx = dgrad(dcb, co.dense.weight)
+            cq, ckv, cctx = br[0]
+            dcctx = dgrad(dcb, _lin(co.dense))
             grads[P + "output.dense.weight"], grads[P + "output.dense.bias"] = wgrad(dcb, cctx, bias=True)
-            dy0, de = _cross_branch_bwd(P + "self.", sms[0], grads, dcctx, cq, ckv, wckv, y02, enc2s[0], B, H, L2, Nk, scale, None, dc0,
+            dy0, de = _cross_branch_bwd(P + "self.", sms[0], grads, dcctx, cq, ckv, y02, enc2s[0], B, H, L2, Nk, scale, None, dc0,
                                         drop=adrop(2))
             denc = de.view(B, Nk, De)
     else:
@@ -988,10 +955,10 @@ def med_layer_backward(layer, hidden, mask2d, token_attn, temperature, k, dy, en
     da0, grads["attention.output.LayerNorm.weight"], grads["attention.output.LayerNorm.bias"] = layernorm_bwd(
         a0, ln1.weight.detach(), dao.contiguous(), ln1.eps)
     dab = hd(da0, 1)
-    dctx = dgrad(dab, so.dense.weight)                                        # a0 = hidden + dropout(ctx Wo^T + bo)
+    dctx = dgrad(dab, _lin(so.dense))                                        # a0 = hidden + dropout(ctx Wo^T + bo)
     grads["attention.output.dense.weight"], grads["attention.output.dense.bias"] = wgrad(dab, ctx, bias=True)
     dqkv = attention_bwd(qkv, dctx, ctx, B, H, L, scale, dnrm, da, dp0, key_mask=mask2d, mask_qk=causal, drop=adrop(0))
-    dh = dgrad(dqkv, wqkv, residual=da0)
+    dh = dgrad(dqkv, _lin(sa.query, sa.key, sa.value), residual=da0)
     gw, gb = wgrad(dqkv, h2, bias=True)
     for i, nm in enumerate(("query", "key", "value")):
         grads[f"attention.self.{nm}.weight"] = gw[i * D:(i + 1) * D]
@@ -1011,9 +978,8 @@ class MedLayerFunction(torch.autograd.Function):
         prune = temperature > 0
         cross = enc0 is not None
         twin = enc1 is not None
-        from .runtime import to_compute
         # encoder tokens as the layer's GEMM operand: f32 in the fp32 mode, f16-split planes in the f16x3 mode
-        flat = lambda e: to_compute(e.reshape(-1, e.shape[-1]).contiguous().float())
+        flat = lambda e: runtime.to_compute(e.reshape(-1, e.shape[-1]).contiguous().float())
         em = enc_masks if enc_masks is not None else (None, None)
         ctx.causal = causal
         ctx.saved = None
@@ -1149,8 +1115,8 @@ class QueryModelFunction(torch.autograd.Function):
             ft = x[:, 1:, :].contiguous()
             if ctx.has_map:
                 wm, bm = ctx.saved_tensors[3], ctx.saved_tensors[4]
-                wmp, bmp = _f32_wb(wm, bm)
-                q = _gemm(ft.view(B * n, D), wmp, bmp, n=wm.shape[0], out_dtype=torch.float32).view(B, n, -1)
+                qmap = train_lin([wm], [bm])
+                q = linear(ft.view(B * n, D), qmap).view(B, n, -1)
             else:
                 q = ft
             dinner = dta.contiguous().float().clone() if dta is not None else torch.zeros_like(ta)
@@ -1163,7 +1129,7 @@ class QueryModelFunction(torch.autograd.Function):
             gmap = ()
             if ctx.has_map:
                 gmap = wgrad(dq2, ft.view(B * n, D), bias=True)
-                dq2 = dgrad(dq2, wm)
+                dq2 = dgrad(dq2, qmap)
             dx = None
             if ctx.needs_input_grad[1]:
                 dx = torch.zeros_like(x)
@@ -1258,7 +1224,6 @@ def module_dropout(module, p, x):
     """nn.Dropout(p) of a mirror module on the HIP path: identity in eval mode / p = 0, else a fresh site of the process-wide counter"""
     if not module.training or p <= 0.0:
         return x
-    from .runtime import next_dropout_base
     seed, base = next_dropout_base()
     return DropoutFunction.apply(x, p, seed, _site(base, 0))
 
@@ -1269,23 +1234,21 @@ class LinearFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, act):
         ctx.mode = _mode()
-        N = w.shape[0]
-        wp, bb = _f32_wb(w, b)
         x = x.contiguous().float()
-        u = _gemm(x, wp, bb, n=N, out_dtype=torch.float32)
-        ctx.act, ctx.has_b = act, b is not None
-        ctx.save_for_backward(x, w, u)
+        u = linear(x, train_lin([w], [b]))
+        ctx.act = act
+        ctx.save_for_backward(x, w, u, b)
         return act_fwd(u, act) if act != hip.ACT_NONE else u
 
     @staticmethod
     def backward(ctx, dy):
-        x, w, u = ctx.saved_tensors
+        x, w, u, b = ctx.saved_tensors
         with torch.no_grad(), _in_mode(ctx.mode):
             dy = dy.contiguous().float()
             du = act_bwd(u, dy, ctx.act) if ctx.act != hip.ACT_NONE else dy
-            dx = dgrad(du, w) if ctx.needs_input_grad[0] else None
+            dx = dgrad(du, train_lin([w], [b])) if ctx.needs_input_grad[0] else None
             dw = wgrad(du, x) if ctx.needs_input_grad[1] else None
-            db = colsum(du) if ctx.has_b else None
+            db = colsum(du) if b is not None else None
         return dx, dw, db, None
 
 
@@ -1325,14 +1288,11 @@ class ClipPatchTokensFunction(torch.autograd.Function):
     def forward(ctx, img, w, cls, pos, patch):
         ctx.mode = _mode()
         cols = hip.patchify(img, patch, torch.float32)
-        w2 = w.reshape(w.shape[0], -1)
-        if cols.shape[1] != w2.shape[1]:  # patch sizes with a zero tail in the patchify rows (ViT-L/14: 588 -> 640 columns)
-            kp = cols.shape[1]
-            wp = _cached(("pwk", w.data_ptr(), _x3(), kp), [w],
-                         _versioned(lambda: _pad_w(torch.nn.functional.pad(w2.detach(), (0, kp - w2.shape[1])))))
+        if cols.shape[1] != w[0].numel():  # patch sizes with a zero tail in the patchify rows (ViT-L/14: 588 -> 640 columns)
+            L = train_lin([w], kp=cols.shape[1])
         else:
-            wp, _ = _f32_wb(w2, None)
-        patches = _gemm(cols, wp, None, out_dtype=torch.float32, n=w.shape[0])
+            L = train_lin([w.reshape(w.shape[0], -1)])
+        patches = linear(cols, L)
         B = img.shape[0]
         ctx.np_, ctx.patch = patches.shape[0] // B, patch
         ctx.save_for_backward(img, w)

@@ -5,6 +5,7 @@ of the hand-written gfx950 kernels behind the C-ABI.  There is NO fallback: if t
 rejects its arguments a RuntimeError is raised.
 """
 import ctypes
+import math
 import os
 from ctypes import c_float, c_int, c_size_t, c_void_p
 
@@ -765,16 +766,19 @@ def split_code(t):
     return F16S if t.dtype == torch.float16 else BF16
 
 
+def weight_log2_scale(amax):
+    """the s of a weight stored as w * 2^s, from the host value of max|w|: max|w| * 2^s in (2^13, 2^14]; 0 for zero, NaN or inf"""
+    if amax > 0 and amax == amax and amax != float("inf"):
+        return max(-100, min(100, 14 - math.ceil(math.log2(amax))))
+    return 0
+
+
 def cast_lp_weight(w):
     """Prepared weight of a fast mode: bf16 cast, or - "f16" mode - f16 of w * 2^s with max|w| * 2^s in (2^13, 2^14] (small
     weights stay clear of the f16 subnormals; the tensor is tagged with the accumulator scale 2^-s like the split planes)."""
     if lp_format() != F16:
         return cast_bf16(w)
-    amax = float(w.abs().max())
-    s = 0
-    if amax > 0 and amax == amax and amax != float("inf"):
-        import math
-        s = max(-100, min(100, 14 - math.ceil(math.log2(amax))))
+    s = weight_log2_scale(float(w.abs().max()))
     dst = cast_bf16(w, scale=2.0 ** s)
     dst._madtp_w_scale = float(2.0 ** -s)
     return dst
@@ -801,14 +805,7 @@ def split_f16_weight(w, log2_scale=None):
     for O(1) activations - their planes are then accurate to ~3e-8 ABSOLUTE, far inside its tolerance."""
     _req(w, torch.float32, "w")
     n, K = w.shape
-    s = 0
-    amax = float(w.abs().max()) if log2_scale is None else 0.0
-    if log2_scale is not None:
-        s = int(log2_scale)
-    elif amax > 0 and amax == amax and amax != float("inf"):
-        import math
-        s = 14 - math.ceil(math.log2(amax))
-        s = max(-100, min(100, s))
+    s = int(log2_scale) if log2_scale is not None else weight_log2_scale(float(w.abs().max()))
     dst = torch.empty((n, 2 * K), device=w.device, dtype=torch.float16)
     _check(load().madtp_split_f16_weight(_p(w), K, _p(dst), n, K, float(2.0 ** s), _stream()), "madtp_split_f16_weight")
     dst._madtp_w_scale = float(2.0 ** -s)

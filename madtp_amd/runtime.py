@@ -181,6 +181,14 @@ def _pad_rows(w):
 SCALE_REUSE = 64
 
 
+def reuse_scale(prev, same_shape):
+    """The reuse rule above.  prev: (log2_scale, age) of the value this preparation replaces in its cache entry, or None; same_shape:
+    the operand keeps its shape.  -> (the s to prepare with, or None: read max|w|; the new value's age)"""
+    if prev is not None and same_shape and prev[0] is not None and prev[1] < SCALE_REUSE:
+        return prev[0], prev[1] + 1
+    return None, 0
+
+
 def prepare_linear(weights, biases, dtype, prev=None):
     """weights: list of [out_i, in] tensors concatenated along out (fused projections); biases likewise (or None).
     prev: the Lin this one replaces in its cache entry (same parameters, an older version) or None."""
@@ -192,8 +200,7 @@ def prepare_linear(weights, biases, dtype, prev=None):
     if dtype == torch.bfloat16:
         w = hip.cast_lp_weight(w.contiguous())
     elif dtype == torch.float16:
-        if prev is not None and prev.log2_scale is not None and prev.age < SCALE_REUSE and prev.w.shape[0] == w.shape[0]:
-            s, age = prev.log2_scale, prev.age + 1
+        s, age = reuse_scale(None if prev is None else (prev.log2_scale, prev.age), prev is not None and prev.w.shape[0] == w.shape[0])
         w = hip.split_f16_weight(w.contiguous(), log2_scale=s)
         s = w._madtp_log2_scale
     b = None

@@ -72,6 +72,107 @@ def test_dgrad_wgrad(hip):
     assert _rel(bw.wgrad(dy, x), (dy.double().t() @ x.double()).float()) < 1e-5
 
 
+LIN_MODES = ["fp32", "f16x3", "bf16", "f16"]  # the last two: the amp route (runtime.training_amp) in either 2-byte element format
+LIN_CASES = {"single": [(132, 64)],            # N no multiple of 64 or 128: the zero padding of both operands
+             "fused": [(64, 128), (68, 128)],  # two parts fused along N: the row offset of the second
+             "fallback": [(2, 64)],            # N % 4 != 0: not for the one-pass plane kernel
+             "k72": [(100, 72)],               # K % 64 != 0: no 2-byte / split forward operand (and K % 32 != 0: no forward GEMM at all)
+             "k96": [(100, 96)]}               # K % 64 != 0 that the exact-f32 GEMM takes: the forward's f32 fallback, run
+
+
+def _lin_mode(mode):
+    import contextlib
+    from madtp_amd import runtime
+    st = contextlib.ExitStack()
+    st.enter_context(runtime.precision(mode))
+    if mode in ("bf16", "f16"):
+        st.enter_context(runtime.training_amp())
+    return st
+
+
+def _values(hip, op, rows, cols):
+    """float64 values [rows, cols] of a prepared weight operand (f32, 2-byte, or f16 planes [Q0 | Q1]) with its scale undone"""
+    if op.dtype == torch.float16:
+        half = op.shape[1] // 2
+        v = op[:, :half].double() + op[:, half:].double()
+    else:
+        v = hip.lp_to_f32(op).double() if op.dtype == torch.bfloat16 else op.double()
+    return v[:rows, :cols] * hip.w_scale_of(op)
+
+
+def _rounded(hip, a, like):
+    """float64 values of the activation operand that rides with the weight operand `like` (only the amp route rounds it visibly)"""
+    return hip.lp_to_f32(hip.cast_bf16(a.contiguous())).double() if like.dtype == torch.bfloat16 else a.double()
+
+
+@pytest.mark.parametrize("case", list(LIN_CASES))
+@pytest.mark.parametrize("mode", LIN_MODES)
+def test_train_lin_operands(hip, mode, case):
+    """backward.TrainLin: `fwd` and `t` hold the bits of the primitives composed by hand (runtime._pad_rows / transpose_pad, then
+    hip.split_f16_weight at the entry's scale or hip.cast_lp_weight), padding is zero, linear / dgrad agree with float64 (amp route:
+    float64 of the rounded operands) to 1e-5, and a [2, 64] weight keeps its f16-split scale across an optimizer step.  In the f16x3
+    mode the "single" and "fused" operands come from the one-pass madtp_weight_planes: the same bits as split_f16_weight.
+    K = 72 has no forward GEMM in any mode (the exact-f32 GEMM reads whole 128-byte slabs, K % 32 == 0), so that case checks the
+    operands and dgrad; K = 96 runs the forward's f32 fallback."""
+    from madtp_amd import backward as bw, runtime
+    shapes = LIN_CASES[case]
+    ws = [torch.nn.Parameter(_rand(n, k, seed=10 + i, scale=0.05).cuda()) for i, (n, k) in enumerate(shapes)]
+    bs = [torch.nn.Parameter(_rand(n, seed=20 + i).cuda()) for i, (n, _) in enumerate(shapes)]
+    cat, bias = torch.cat([w.detach() for w in ws], 0), torch.cat([b.detach() for b in bs], 0)
+    N, K = cat.shape
+    pad = lambda n, m: (n + m - 1) // m * m
+    Np = pad(N, 32 if mode == "fp32" else 64)
+    a, dy = _rand(70, K, seed=30).cuda(), _rand(70, N, seed=31).cuda()
+    with _lin_mode(mode):
+        L = bw.train_lin(ws, bs)
+        assert (L.n, L.k) == (N, K) and torch.equal(L.b, bias) and bw.train_lin(ws, bs) is L
+        fwd32, t32 = runtime._pad_rows(cat), bw.transpose_pad(cat, Np, pad(K, 128))
+        if mode == "fp32":
+            want_fwd, want_t = fwd32, t32
+        elif mode == "f16x3":
+            assert L.t._madtp_log2_scale == L.log2_scale == hip.weight_log2_scale(float(cat.abs().max())) and L.age == 0
+            want_fwd = hip.split_f16_weight(fwd32, log2_scale=L.log2_scale) if K % 64 == 0 else fwd32
+            want_t = hip.split_f16_weight(t32, log2_scale=L.log2_scale)
+        else:
+            want_fwd, want_t = (hip.cast_lp_weight(fwd32) if K % 64 == 0 else fwd32), hip.cast_lp_weight(t32)
+        for got, want in ((L.t, want_t), (L.fwd, want_fwd)):
+            assert got.dtype == want.dtype and got.shape == want.shape and torch.equal(got, want)
+            assert hip.w_scale_of(got) == hip.w_scale_of(want)
+        assert L.fwd.shape[0] == pad(N, 128) and L.t.shape[0] == pad(K, 128)
+        zero = lambda t: t.numel() == 0 or float(t.float().abs().max()) == 0
+        tcols = L.t.view(L.t.shape[0], -1, Np)  # (planes: [Q0 | Q1], each Np wide)
+        assert tcols.shape[1] == (2 if mode == "f16x3" else 1)
+        assert zero(L.fwd[N:]) and zero(L.t[K:]) and zero(tcols[:, :, N:])
+        if K % 32 == 0:
+            res = _rand(70, N, seed=32).cuda()
+            ref = _rounded(hip, a, L.fwd) @ _values(hip, L.fwd, N, K).t() + bias.double()
+            assert _rel(bw.linear(a, L).double(), ref) < 1e-5
+            assert _rel(bw.linear(a, L, residual=res).double(), ref + res.double()) < 1e-5
+            if mode in ("fp32", "f16x3"):
+                assert _rel(ref, a.double() @ cat.double().t() + bias.double()) < 1e-5
+        dyp = torch.zeros(70, Np, device="cuda")
+        dyp[:, :N] = dy
+        ref = (_rounded(hip, dyp, L.t) @ _values(hip, L.t, K, Np).t())
+        assert _rel(bw.dgrad(dy, L).double(), ref) < 1e-5
+        if mode in ("fp32", "f16x3"):
+            assert _rel(bw.dgrad(dy, L).double(), dy.double() @ cat.double()) < 1e-5
+        if case == "fallback":  # the plain-weight form: its own bias-free entry; in the f16x3 mode the scale survives an optimizer step
+            w = ws[0]
+            assert _rel(bw.dgrad(dy, w).double(), ref) < 1e-5
+            L0 = bw.train_lin([w])
+            assert L0 is not L and L0.age == 0 and (L0.log2_scale is not None) == (mode == "f16x3")
+            w.grad = -w.detach().clone()
+            torch.optim.SGD([w], lr=1.0).step()  # w <- 2 w: a fresh scale would be one less
+            got = bw.dgrad(dy, w)
+            L1 = bw.train_lin([w])
+            assert L1 is not L0 and _rel(got.double(), _rounded(hip, dyp, L1.t) @ _values(hip, L1.t, K, Np).t()) < 1e-5
+            if mode in ("fp32", "f16x3"):
+                assert _rel(got.double(), 2 * dy.double() @ cat.double()) < 1e-5
+            if mode == "f16x3":
+                assert (L1.age, L1.log2_scale) == (1, L0.log2_scale) and L1.log2_scale == hip.weight_log2_scale(float(w.detach().abs().max())) + 1
+                assert torch.equal(L1.t, hip.split_f16_weight(bw.transpose_pad(w.detach(), Np, pad(K, 128)), log2_scale=L0.log2_scale))
+
+
 def test_transpose_split_equals_transpose_then_split(hip):
     """madtp_transpose_split (one pass) writes the bits of madtp_transpose_pad + madtp_split_f16 / madtp_split_f16_weight(scale 1),
     zero padding included - the operands of the f16x3 weight gradient."""
@@ -249,14 +350,13 @@ def test_f16x3_weight_planes_survive_forward_backward_alternation(hip):
     opt = torch.optim.SGD(blk.parameters(), lr=1e-3)
     _fwd_bwd(blk, "f16x3")
     opt.step()
-    w = blk.mlp.fc1.weight
     _fwd_bwd(blk, "f16x3")
     with _train_mode("f16x3"):
-        o1 = bw._x3_weights(("x3w", w.data_ptr(), tuple(w.shape)), [w])
+        o1 = bw._lin(blk.mlp.fc1)
     age = o1.age
     _fwd_bwd(blk, "f16x3")
     with _train_mode("f16x3"):
-        o2 = bw._x3_weights(("x3w", w.data_ptr(), tuple(w.shape)), [w])
+        o2 = bw._lin(blk.mlp.fc1)
     assert o2 is o1 and o2.age == age == 1
 
 
