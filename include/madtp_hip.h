@@ -45,7 +45,9 @@ extern "C" {
 #define MADTP_ACT_QUICK_GELU 2 /* x*sigmoid(1.702x): clip/model.py:169-171               */
 #define MADTP_ACT_RELU 3       /* cls_head: blip_nlvr.py:59                              */
 
-/* Library/version probe; returns the ABI version (increments on any signature change). */
+/* Library/version probe; returns the ABI version (increments on any signature change).  The Python binding (madtp_amd/abi.py)
+ * reads this header - prototypes, structs and the integer defines - so an entry point is declared here and nowhere else. */
+#define MADTP_ABI_VERSION 31
 int madtp_abi_version(void);
 /* Human-readable name of a negative MADTP_E_* code. */
 const char* madtp_strerror(int code);

@@ -565,7 +565,7 @@ def _vit_block_fwd(blk, x, token_attn, temperature, k, mask_qk=None, max_keep=0,
     score = dst_pos = merge_w = info = None
     if prune and k is None:
         score, thr, count, kk = hip.token_score_sync(side, token_attn, temperature, B, H, N)
-        info = {"k": kk, "score": score, "threshold": thr, "count": count, "pruned": False, "indices": None, "indices_sort": None}
+        info = hip.prune_info(kk, score, thr, count)
         k = 0 if (kk <= max_keep or (N - 1 - kk) <= 1) else kk
     elif prune:
         score, _, _, _ = hip.token_score(side, token_attn, temperature, B, H, N)
@@ -573,7 +573,7 @@ def _vit_block_fwd(blk, x, token_attn, temperature, k, mask_qk=None, max_keep=0,
     if k > 0:
         indices, indices_sort, dst_pos, merge_w = hip.token_select(score, k)
         if info is not None:
-            info.update(pruned=True, indices=indices, indices_sort=indices_sort)
+            info = hip.prune_info(kk, score, thr, count, indices, indices_sort)
         y0 = hip.token_gather(x_attn.view(B, N, D), dst_pos, merge_w, k)
     else:
         y0 = x_attn.view(B, N, D)
@@ -811,7 +811,7 @@ def _med_layer_fwd(layer, hidden, mask2d, token_attn, temperature, k, enc=None, 
     score = dst_pos = merge_w = info = mask_out = None
     if prune and k is None:
         score, thr, count, kk = hip.token_score_sync(side, token_attn, temperature, B, H, L)
-        info = {"k": kk, "score": score, "threshold": thr, "count": count, "pruned": False, "indices": None, "indices_sort": None}
+        info = hip.prune_info(kk, score, thr, count)
         k = 0 if (kk < 1 or (L - 1 - kk) <= 1) else kk
     elif prune:
         score, _, _, _ = hip.token_score(side, token_attn, temperature, B, H, L)
@@ -819,7 +819,7 @@ def _med_layer_fwd(layer, hidden, mask2d, token_attn, temperature, k, enc=None, 
     if k > 0:
         indices, indices_sort, dst_pos, merge_w = hip.token_select(score, k)
         if info is not None:
-            info.update(pruned=True, indices=indices, indices_sort=indices_sort)
+            info = hip.prune_info(kk, score, thr, count, indices, indices_sort)
             if mask2d is not None:  # the pruned sequence's additive mask (nlvr_encoder.py:451-452 / med.py:386-389)
                 mask_out = (hip.mask_gather(mask2d, indices_sort, k) if getattr(layer, "variant", "") == "nlvr"
                             else hip.mask_gather(mask2d, indices, k, indices_sort))

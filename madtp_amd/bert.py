@@ -261,13 +261,11 @@ class _BertLayerBase(nn.Module):
         sa = self.attention.self
         score, thr, count, kmax = hip.token_score(sa.score_side, token_attn, temperature, B, sa.num_attention_heads, L)
         k = int(kmax.item())
-        info = {"k": k, "score": score, "threshold": thr, "count": count, "pruned": False, "indices": None,
-                "indices_sort": None}
-        self.last_prune = info
+        self.last_prune = hip.prune_info(k, score, thr, count)
         if k < 1 or (n - k) <= 1:
             return x, mask
         indices, indices_sort, dst_pos, merge_w = hip.token_select(score, k)
-        info.update(pruned=True, indices=indices, indices_sort=indices_sort)
+        self.last_prune = hip.prune_info(k, score, thr, count, indices, indices_sort)
         y = hip.token_gather(x, dst_pos, merge_w, k)
         if mask is not None:
             if self.variant == "nlvr":

@@ -450,7 +450,7 @@ extern "C" int madtp_split_f16_weight(const float* w, int ldw, void* dst, int n,
     return 0;
 }
 
-extern "C" int madtp_abi_version(void) { return 31; }
+extern "C" int madtp_abi_version(void) { return MADTP_ABI_VERSION; }
 
 extern "C" const char* madtp_strerror(int code) {
     switch (code) {

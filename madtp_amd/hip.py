@@ -7,187 +7,30 @@ rejects its arguments a RuntimeError is raised.
 import ctypes
 import math
 import os
-from ctypes import c_float, c_int, c_size_t, c_void_p
+from ctypes import c_float, c_int, c_void_p
 
 import torch
 
-F32, BF16, F16S, F16 = 0, 1, 2, 3  # F16S: f16-split operand planes of the fp32-accurate GEMM (include/madtp_hip.h), torch.float16
-#                                    F16: plain IEEE f16 operands (the "f16" fast mode), see set_lp_format below
-ACT_NONE, ACT_GELU, ACT_QUICK_GELU, ACT_RELU = 0, 1, 2, 3
-ABI_VERSION = 31
+from . import abi
+
+
+def _defs(prefix, names):
+    """the header's integer defines MADTP_<prefix><name>, in the order of `names`"""
+    return tuple(abi.DEFINES["MADTP_" + prefix + n] for n in names.split())
+
+
+# Signatures, struct layouts and constants all come from include/madtp_hip.h (madtp_amd/abi.py): a new entry point is declared there only.
+F32, BF16, F16S, F16 = _defs("", "F32 BF16 F16S F16")  # F16S: f16-split operand planes of the fp32-accurate GEMM, torch.float16
+#                                                       F16: plain IEEE f16 operands (the "f16" fast mode), see set_lp_format below
+ACT_NONE, ACT_GELU, ACT_QUICK_GELU, ACT_RELU = _defs("ACT_", "NONE GELU_ERF QUICK_GELU RELU")
+ABI_VERSION, E_RANGE = _defs("", "ABI_VERSION E_RANGE")
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libmadtp_hip.so")
 
-_SIGS = {
-    "madtp_abi_version": (c_int, []),
-    "madtp_strerror": (ctypes.c_char_p, [c_int]),
-    "madtp_profile_begin": (c_int, []),
-    "madtp_profile_end": (c_int, [ctypes.c_char_p, c_int]),
-    "madtp_gemm": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_int, c_int, c_int, c_float, c_float, c_void_p]),
-    "madtp_gemm_set_config": (c_int, [c_int]),
-    "madtp_gemm_plan": (c_int, [c_int] * 11 + [c_void_p, c_void_p, c_int]),
-    "madtp_attention_plan": (c_int, [c_int] * 14 + [c_void_p, c_int]),
-    "madtp_stream_create_cumask": (c_int, [c_void_p, c_void_p, c_int]),
-    "madtp_stream_set_sched": (c_int, [c_void_p, c_int, c_float, c_int]),
-    "madtp_stream_get_sched": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
-    "madtp_stream_destroy": (c_int, [c_void_p]),
-    "madtp_set_score_fast": (c_int, [c_int]),
-    "madtp_gemm_splitk": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "madtp_splitk_ln": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
-                                c_float, c_float, c_float, c_void_p]),
-    "madtp_layernorm": (c_int, [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_void_p]),
-    "madtp_patchify": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "madtp_assemble_tokens": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p]),
-    "madtp_bert_embed": (c_int, [c_void_p] * 7 + [c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    "madtp_attention": (c_int, [c_void_p] * 8 + [c_int] * 8 + [c_float, c_int, c_void_p]),
-    "madtp_attention_qk_mask": (c_int, [c_void_p] * 6 + [c_int] + [c_void_p] * 3 + [c_int] * 8 + [c_float, c_int, c_void_p]),
-    "madtp_token_score": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float]
-                          + [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p]),
-    "madtp_token_select": (c_int, [c_void_p, c_int] + [c_void_p] * 4 + [c_int, c_int, c_void_p]),
-    "madtp_token_gather": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
-    "madtp_token_gather_ln": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p]),
-    "madtp_mask_gather": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "madtp_query_att_ft": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_float, c_int,
-                                   c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
-    "madtp_align_logits": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
-    "madtp_vector_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "madtp_vit_block_workspace": (c_size_t, [c_int] * 6),
-    "madtp_vit_block_attn": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p, c_int, c_int,
-                                     c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "madtp_vit_block_mlp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p,
-                                    c_void_p, c_void_p, c_void_p]),
-    "madtp_query_model": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p, c_void_p, c_void_p,
-                                  c_int, c_float, c_int, c_int, c_int, c_void_p]),
-    "madtp_bert_layer_workspace": (c_size_t, [c_int] * 7),
-    "madtp_bert_layer_attn": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_int,
-                                      c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
-                                      c_void_p]),
-    "madtp_bert_layer_rest": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int,
-                                      c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
-                                      c_void_p, c_void_p]),
-    "madtp_token_score_sync": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float]
-                               + [c_void_p] * 4 + [c_int, c_int, c_int, c_void_p]),
-    "madtp_token_score_publish": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float]
-                                  + [c_void_p] * 3 + [c_int, c_int, c_int, c_void_p, c_void_p]),
-    "madtp_token_score_wait": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p]),
-    "madtp_attention_indexed": (c_int, [c_void_p] * 9 + [c_int] * 8 + [c_float, c_int, c_void_p]),
-    "madtp_vit_block": (c_int, [c_void_p] * 5 + [c_size_t, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float]
-                        + [c_void_p] * 7 + [c_void_p]),
-    "madtp_vit_block_keep": (c_int, [c_void_p] * 5 + [c_size_t, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float]
-                             + [c_void_p] * 5 + [c_int] + [c_void_p] * 2 + [c_void_p]),
-    "madtp_bert_layer": (c_int, [c_void_p] * 7 + [c_size_t, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float]
-                         + [c_void_p] * 5 + [c_int] + [c_void_p] * 9 + [c_int] + [c_void_p] * 3),
-    "madtp_vit_encoder": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_float, c_void_p]),
-    "madtp_vit_encoder_async": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_float, c_void_p,
-                                         c_void_p, c_void_p]),
-    "madtp_bert_encoder": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int,
-                                   c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                   c_void_p]),
-    "madtp_bert_encoder_async": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int,
-                                         c_int, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
-                                         c_void_p, c_void_p, c_void_p]),
-    "madtp_bert_decode_step": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
-                                       c_void_p, c_void_p, c_size_t, c_void_p]),
-    "madtp_kv_cache_reorder": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
-    "madtp_sample_top_p": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
-                                   c_int, c_void_p]),
-    "madtp_add_scale": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_size_t, c_void_p]),
-    "madtp_gemm_pair": (c_int, [c_void_p] * 8 + [c_int] * 8 + [c_float, c_float, c_void_p]),
-    "madtp_attention_pair": (c_int, [c_void_p] * 11 + [c_int] * 8 + [c_float, c_int, c_void_p]),
-    "madtp_query_att_ft_multi": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p]),
-    "madtp_query_att_ft_multi_split": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_int, c_int, c_void_p]),
-    "madtp_cast_bf16": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
-    "madtp_cast_lp": (c_int, [c_void_p, c_void_p, c_size_t, c_int, c_float, c_void_p]),
-    "madtp_range_status": (c_int, [c_int, c_void_p]),
-    "madtp_split_f16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "madtp_split_f16_weight": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_void_p]),
-    "madtp_lm_loss": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_float, c_void_p, c_int, c_void_p]),
-    "madtp_token_prob": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
-    "madtp_beam_topk": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
-    "madtp_beam_topk_penalty": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_void_p,
-                                         c_void_p, c_int, c_void_p]),
-    # backward of the pruned ViT block (csrc/backward.hip)
-    "madtp_transpose_pad": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
-    "madtp_gemm_splitk_pp": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
-    "madtp_splitk_sum": (c_int, [c_void_p, c_int, c_size_t, c_void_p, c_void_p]),
-    "madtp_beam_update": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double, c_int, c_int, c_int, c_int, c_int,
-                                  c_void_p]),
-    "madtp_weight_planes": (c_int, [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
-    "madtp_transpose_split": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "madtp_colsum": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
-    "madtp_act_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
-    "madtp_layernorm_bwd": (c_int, [c_void_p] * 8 + [c_int, c_int, c_float, c_void_p]),
-    # retrieval training step (csrc/retrieval.hip)
-    "madtp_itc_workspace": (c_size_t, [c_int, c_int, c_int]),
-    "madtp_itc_loss": (c_int, [c_void_p] * 7 + [c_float] + [c_void_p] * 4 + [c_size_t, c_int, c_int, c_int, c_void_p]),
-    "madtp_ema_blocks": (c_int, [ctypes.c_int64]),
-    "madtp_ema_update": (c_int, [c_void_p, c_int, c_int, c_float, c_float, c_void_p]),
-    "madtp_itm_negatives": (c_int, [c_void_p] * 10 + [c_int, c_int, c_int, c_void_p]),
-    # CLIP's text embedding under autograd (csrc/clip.hip)
-    "madtp_clip_embed": (c_int, [c_void_p] * 4 + [c_int, c_int, c_int, c_int, c_void_p]),
-    "madtp_embedding_grad_workspace": (c_size_t, [c_int]),
-    "madtp_embedding_grad": (c_int, [c_void_p] * 4 + [c_size_t, c_int, c_int, c_int, c_void_p]),
-    # retrieval evaluation (csrc/eval.hip)
-    "madtp_rank_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "madtp_rank_embeds": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 6 + [c_size_t, c_void_p]),
-    "madtp_rank_scores": (c_int, [c_void_p, c_int, c_int, c_int] + [c_void_p] * 5),
-    # the optimizer step (csrc/optim.hip)
-    "madtp_adamw_blocks": (c_int, [ctypes.c_int64]),
-    "madtp_adamw_step": (c_int, [c_void_p, c_int, c_int] + [c_float] * 7 + [c_void_p]),
-    "madtp_token_gather_bwd": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p]),
-    "madtp_token_score_bwd": (c_int, [c_void_p] * 5 + [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4
-                              + [c_int, c_int, c_int, c_void_p]),
-    "madtp_attention_probs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
-    "madtp_attention_probs_x": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
-                                        c_float, c_void_p]),
-    "madtp_att_ft_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
-    "madtp_attention_bwd_workspace": (c_size_t, [c_int, c_int, c_int]),
-    "madtp_attention_bwd_cross_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
-    "madtp_attention_bwd_cross": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
-                                          c_void_p, c_int, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_float, c_float, ctypes.c_uint64,
-                                          ctypes.c_uint64, c_void_p]),
-    "madtp_attention_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 6
-                            + [c_int, c_void_p, c_size_t, c_void_p, c_int, c_int, c_int, c_float, c_float, ctypes.c_uint64, ctypes.c_uint64, c_void_p]),
-    "madtp_dropout": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_float, ctypes.c_uint64, ctypes.c_uint64, c_void_p]),
-    "madtp_attention_train": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
-                                      c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, ctypes.c_uint64, ctypes.c_uint64, c_void_p]),
-}
-
-
-
-class LinStruct(ctypes.Structure):
-    _fields_ = [("w", c_void_p), ("b", c_void_p), ("n", c_int), ("k", c_int), ("w_scale", c_float)]
-
-
-class VitBlockW(ctypes.Structure):
-    _fields_ = [("ln1_g", c_void_p), ("ln1_b", c_void_p), ("ln2_g", c_void_p), ("ln2_b", c_void_p),
-                ("eps", c_float), ("scale", c_float),
-                ("qkv", LinStruct), ("proj", LinStruct), ("fc1", LinStruct), ("fc2", LinStruct),
-                ("heads", c_int), ("dim", c_int), ("dtype", c_int), ("act", c_int), ("attn_mask", c_void_p), ("ld_attn_mask", c_int)]
-
-
-class BertLayerW(ctypes.Structure):
-    _fields_ = [("qkv", LinStruct), ("attn_out", LinStruct), ("ln_att_g", c_void_p), ("ln_att_b", c_void_p),
-                ("cross", c_int), ("variant_nlvr", c_int), ("has_merge", c_int),
-                ("cq", LinStruct * 2), ("ckv", LinStruct * 2), ("cdense", LinStruct * 2), ("merge", LinStruct),
-                ("fused_twin", c_int), ("cq_fused", LinStruct), ("cdense_fused", LinStruct),
-                ("ln_cross_g", c_void_p), ("ln_cross_b", c_void_p),
-                ("inter", LinStruct), ("out", LinStruct), ("ln_out_g", c_void_p), ("ln_out_b", c_void_p),
-                ("eps", c_float), ("scale", c_float), ("heads", c_int), ("dim", c_int), ("dtype", c_int),
-                ("self_mask_qk", c_void_p), ("ld_self_mask_qk", c_int)]
-
-
-class QueryW(ctypes.Structure):
-    _fields_ = [("sd_w", c_void_p), ("sd_hi", c_void_p), ("sd_lo", c_void_p), ("split_dtype", c_int), ("sd_scale", c_float),
-                ("K", c_int), ("inv_sqrt_sd", c_float), ("att_ft", c_void_p), ("stats_ws", c_void_p)]
-
-
-class LayerIO(ctypes.Structure):
-    _fields_ = [("logits", c_void_p), ("x_attn", c_void_p), ("y", c_void_p), ("y_lp", c_void_p), ("mask_out", c_void_p),
-                ("score", c_void_p), ("threshold", c_void_p), ("count", c_void_p), ("indices", c_void_p),
-                ("indices_sort", c_void_p), ("k_out", c_int), ("k_used", c_int), ("n_out", c_int)]
+# the header's structs, fields in its order (AttFtSeg(*t) and QueryW(...) are built positionally)
+LinStruct, VitBlockW, BertLayerW, QueryW, LayerIO, AttFtSeg = (abi.STRUCTS[n] for n in (
+    "madtp_lin", "madtp_vit_block_w", "madtp_bert_layer_w", "madtp_query_w", "madtp_layer_io", "madtp_att_ft_seg"))
 
 
 def lin_struct(lin):
@@ -200,7 +43,7 @@ _lib = None
 
 
 def exported_symbols():
-    return sorted(_SIGS)
+    return sorted(abi.SIGNATURES)
 
 
 def load(path=None):
@@ -213,7 +56,7 @@ def load(path=None):
         raise RuntimeError(f"{path} not found - run `python -m madtp_amd.build` (hipcc, gfx950). "
                            "There is no CPU/eager fallback for the product path.")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in _SIGS.items():
+    for name, (res, args) in abi.SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError => header/library mismatch
         fn.restype = res
         fn.argtypes = args
@@ -223,9 +66,6 @@ def load(path=None):
     _lib = lib
     lib.madtp_set_score_fast(_score_fast)
     return lib
-
-
-E_RANGE = -6
 
 
 def _check(code, what):
@@ -337,7 +177,7 @@ class gemm_config:
         load().madtp_gemm_set_config(self.prev)
 
 
-PLAN_PAIR, PLAN_BIAS, PLAN_RESIDUAL, PLAN_M_DEV = 1, 2, 4, 8
+PLAN_PAIR, PLAN_BIAS, PLAN_RESIDUAL, PLAN_M_DEV = _defs("PLAN_", "PAIR BIAS RESIDUAL M_DEV")
 PLAN_FIELDS = ("status", "kernel", "variant", "rows", "cols", "ntm", "ntn", "ngrp", "grid", "lds", "sk", "desc", "fast_epi", "om", "mode")
 
 
@@ -353,10 +193,14 @@ def gemm_plan(M, N, K, lda, ldw, ldc, ldr, ab_dtype, c_dtype, splitk=1, flags=0,
 # flags of madtp_attention_plan (include/madtp_hip.h MADTP_ATTN_PLAN_*), its resource bits and the fields it writes
 (ATTN_PLAN_PAIR, ATTN_PLAN_SCORES, ATTN_PLAN_MASK_QK, ATTN_PLAN_ADD_MASK, ATTN_PLAN_KV_INDEX, ATTN_PLAN_N_DEV, ATTN_PLAN_DEV_Q_ONLY,
  ATTN_PLAN_NULL_PTR, ATTN_PLAN_NO_P0, ATTN_PLAN_NO_ONORM, ATTN_PLAN_QKV_UNALIGNED, ATTN_PLAN_OUT_UNALIGNED16, ATTN_PLAN_OUT_UNALIGNED8,
- ATTN_PLAN_PAIR_UNALIGNED, ATTN_PLAN_PAIR_MASKS_DIFFER) = (1 << i for i in range(15))
-ATTN_RES_HM, ATTN_RES_OPART = 1, 2
+ ATTN_PLAN_PAIR_UNALIGNED, ATTN_PLAN_PAIR_MASKS_DIFFER) = _defs(
+    "ATTN_PLAN_", "PAIR SCORES MASK_QK ADD_MASK KV_INDEX N_DEV DEV_Q_ONLY NULL_PTR NO_P0 NO_ONORM QKV_UNALIGNED OUT_UNALIGNED16 OUT_UNALIGNED8 "
+    "PAIR_UNALIGNED PAIR_MASKS_DIFFER")
+ATTN_RES_HM, ATTN_RES_OPART = _defs("ATTN_RES_", "HM OPART")
 ATTN_PLAN_FIELDS = ("status", "family", "nt", "storage", "scores", "f16", "hs", "rb", "hv", "gx", "gy", "gz", "block", "lds", "lds_optin", "need_hm",
                     "need_opart", "split_dim")
+if (len(PLAN_FIELDS), len(ATTN_PLAN_FIELDS)) != _defs("", "PLAN_FIELDS ATTN_PLAN_FIELDS"):
+    raise RuntimeError("hip.PLAN_FIELDS / ATTN_PLAN_FIELDS disagree with MADTP_PLAN_FIELDS / MADTP_ATTN_PLAN_FIELDS of include/madtp_hip.h")
 ATTN_FAMILIES = ("attn_kernel", "attn_f16s_kernel", "attn_bf16_kernel", "attn_bf16_small_kernel", "attn_large_kernel", "attn_large_f16s_kernel",
                  "attn_bf16_large_kernel")
 ATTN_PAIR_TWO_LAUNCHES = 1000  # status: madtp_attention_pair runs this pair as two launches
@@ -700,11 +544,6 @@ def query_att_ft(token_attn, ft, out=None, sd_dim=768, fast=False):
     return out
 
 
-class AttFtSeg(ctypes.Structure):
-    _fields_ = [("token_attn", c_void_p), ("ft", c_void_p), ("n", c_int), ("ldt_row", c_int), ("ldt_batch", c_int),
-                ("ldf_row", c_int), ("ldf_batch", c_int)]
-
-
 def query_att_ft_multi(pairs, out=None, sd_dim=768, exact=False):
     """pairs: list of (token_attn [B,n,K] view, ft [B,n,dim] f32 view) of the layers of an encoder -> their summed att_ft
     [B,K,dim] in one launch (fast mode: bf16 MFMA; exact=True: the exact-f32 kernel, bit-identical to summing layer by layer;
@@ -869,35 +708,59 @@ def _carve(buf, *shape):
     return buf.view(-1)[:n].view(*shape)
 
 
+def prune_info(k, score, threshold, count, indices=None, indices_sort=None):
+    """The prune record of a layer (`last_prune`): k = max_b count, the score / threshold / count tensors and, when the layer was
+    pruned, the kept token ids and the full descending order."""
+    return {"k": k, "score": score, "threshold": threshold, "count": count, "pruned": indices is not None, "indices": indices,
+            "indices_sort": indices_sort}
+
+
+def _vit_ws(w, B, N, device):
+    return workspace(load().madtp_vit_block_workspace(B, N, w.dim, w.fc1.n, w.heads, w.dtype), device)
+
+
+def _bert_ws_bytes(w, B, L, Nk):
+    return load().madtp_bert_layer_workspace(B, L, Nk, w.dim, w.inter.n, w.heads, w.dtype)
+
+
+def _bert_ws(w, B, L, Nk, device):
+    return workspace(_bert_ws_bytes(w, B, L, Nk), device)
+
+
+def _score_args(token_attn, temperature, B, n, device):
+    """The pruning-score arguments of a layer-level call - (token_attn, ldt_row, ldt_batch, K, temperature, score, threshold, count)
+    as the library takes them - and the prune_outputs() behind the last three.  temperature <= 0 (no scores): the null pointers
+    and zeros that mean "not computed", and None."""
+    if temperature > 0:
+        ta = _ta_view(token_attn)
+        po = prune_outputs(B, n, device)
+        return ta + (float(temperature), _p(po[0]), _p(po[1]), _p(po[2])), po
+    return (0, 0, 0, 0, 0.0, 0, 0, 0), None
+
+
 def vit_block(wstruct, x, token_attn, temperature, max_keep=0):
     """Block.forward in ONE library call (attention half, host read of k, pruning rule, MLP half).
-    -> (y [B,N',D], info or None); info = dict(k, score, threshold, count, pruned, indices, indices_sort).
+    -> (y [B,N',D], info or None); info = prune_info(...).
     max_keep: CLIP's rule (clip/model.py:220-221: no pruning when k <= max_keep); 0 is the BLIP rule k < 1."""
     B, N, D = x.shape
-    lib = load()
-    nbytes = lib.madtp_vit_block_workspace(B, N, wstruct.dim, wstruct.fc1.n, wstruct.heads, wstruct.dtype)
-    ws = workspace(nbytes, x.device)
+    ws = _vit_ws(wstruct, B, N, x.device)
     x_attn = torch.empty_like(x)
     ybuf = torch.empty_like(x)
     k_out, k_used = ctypes.c_int(0), ctypes.c_int(0)
-    if temperature > 0:
-        tp, ldr, ldb, K = _ta_view(token_attn)
-        score, thr, count, _ = prune_outputs(B, N - 1, x.device)
+    sargs, po = _score_args(token_attn, temperature, B, N - 1, x.device)
+    idx = idx_sort = None
+    if po is not None:
         idx = torch.empty((B, N - 1), device=x.device, dtype=torch.int64)
         idx_sort = torch.empty((B, N - 1), device=x.device, dtype=torch.int64)
-        _check(lib.madtp_vit_block_keep(ctypes.byref(wstruct), _p(x), _p(x_attn), _p(ybuf), _p(ws), ws.numel(), B, N, tp, ldr, ldb,
-                                        K, float(temperature), _p(score), _p(thr), _p(count), _p(idx), _p(idx_sort), int(max_keep),
-                                        ctypes.byref(k_out), ctypes.byref(k_used), _stream()), "madtp_vit_block_keep")
-        info = {"k": k_out.value, "score": score, "threshold": thr, "count": count, "pruned": False, "indices": None,
-                "indices_sort": None}
-        if k_used.value > 0:
-            k = k_used.value
-            info.update(pruned=True, indices=_carve(idx, B, k), indices_sort=idx_sort)
-            return _carve(ybuf, B, k + 2, D), info
-        return ybuf, info
-    _check(lib.madtp_vit_block(ctypes.byref(wstruct), _p(x), _p(x_attn), _p(ybuf), _p(ws), ws.numel(), B, N, 0, 0, 0, 0, 0.0,
-                               0, 0, 0, 0, 0, ctypes.byref(k_out), ctypes.byref(k_used), _stream()), "madtp_vit_block")
-    return ybuf, None
+    _check(load().madtp_vit_block_keep(ctypes.byref(wstruct), _p(x), _p(x_attn), _p(ybuf), _p(ws), ws.numel(), B, N, *sargs, _p(idx),
+                                       _p(idx_sort), int(max_keep) if po is not None else 0, ctypes.byref(k_out),
+                                       ctypes.byref(k_used), _stream()), "madtp_vit_block_keep")
+    if po is None:
+        return ybuf, None
+    k = k_used.value
+    if k > 0:
+        return _carve(ybuf, B, k + 2, D), prune_info(k_out.value, *po[:3], _carve(idx, B, k), idx_sort)
+    return ybuf, prune_info(k_out.value, *po[:3])
 
 
 def bert_layer(wstruct, hidden, mask2d, token_attn, temperature, cross_mode, enc0, enc1, Nk, enc_mask0, enc_mask1,
@@ -905,72 +768,54 @@ def bert_layer(wstruct, hidden, mask2d, token_attn, temperature, cross_mode, enc
     """BertLayer.forward in ONE library call.  -> (y [B,L',D], mask_out [B,L'] or None, info or None, y_lp).
     hidden_lp / y_lp: bf16 copies of the layer input / output (fast mode; the LayerNorms emit them, saving the casts)."""
     B, L, D = hidden.shape
-    lib = load()
     kv_ld = 0
     for t in kv_pre:  # cached [k|v] rows may be column slices of a wider projection (all layers side by side)
         if t is not None:
             if t.stride(-1) != 1 or (kv_ld and kv_ld != t.stride(0)):
                 raise RuntimeError("bert_layer: kv_pre tensors must be row-major with one common row stride")
             kv_ld = t.stride(0)
-    nbytes = lib.madtp_bert_layer_workspace(B, L, Nk, wstruct.dim, wstruct.inter.n, wstruct.heads, wstruct.dtype)
-    ws = workspace(nbytes, hidden.device)
+    dev = hidden.device
+    ws = _bert_ws(wstruct, B, L, Nk, dev)
     att = torch.empty_like(hidden)
     ybuf = torch.empty_like(hidden)
     k_out, k_used = ctypes.c_int(0), ctypes.c_int(0)
-    dev = hidden.device
     ylp = None
     if wstruct.dtype != F32:  # compute-dtype copy of the layer output for the next layer (bf16, or f16-split planes)
         ylp = _lp_empty(hidden.shape, dev, torch.float16 if wstruct.dtype == F16S else torch.bfloat16)
-    if temperature > 0:
-        tp, ldr, ldb, K = _ta_view(token_attn)
-        score, thr, count, _ = prune_outputs(B, L - 1, dev)
+    sargs, po = _score_args(token_attn, temperature, B, L - 1, dev)
+    idx = idx_sort = mbuf = None
+    if po is not None:
         idx = torch.empty((B, L - 1), device=dev, dtype=torch.int64)
         idx_sort = torch.empty((B, L - 1), device=dev, dtype=torch.int64)
         mbuf = torch.empty((B, L), device=dev, dtype=torch.float32) if mask2d is not None else None
-        _check(lib.madtp_bert_layer(ctypes.byref(wstruct), _p(hidden), _p(mask2d), _p(att), _p(ybuf), _p(mbuf), _p(ws), ws.numel(),
-                                    B, L, Nk, tp, ldr, ldb, K, float(temperature), _p(score), _p(thr), _p(count), _p(idx),
-                                    _p(idx_sort), int(cross_mode), _p(enc0), _p(enc1), _p(enc_mask0), _p(enc_mask1),
-                                    _p(hidden_lp), _p(ylp), _p(kv_pre[0]), _p(kv_pre[1]), _p(kv_index), kv_ld, ctypes.byref(k_out),
-                                    ctypes.byref(k_used), _stream()), "madtp_bert_layer")
-        info = {"k": k_out.value, "score": score, "threshold": thr, "count": count, "pruned": False, "indices": None,
-                "indices_sort": None}
-        if k_used.value > 0:
-            k = k_used.value
-            info.update(pruned=True, indices=_carve(idx, B, k), indices_sort=idx_sort)
-            return (_carve(ybuf, B, k + 2, D), (_carve(mbuf, B, k + 2) if mbuf is not None else None), info,
-                    _carve(ylp, B, k + 2, ylp.shape[-1]) if ylp is not None else None)
-        return ybuf, None, info, ylp
-    _check(lib.madtp_bert_layer(ctypes.byref(wstruct), _p(hidden), _p(mask2d), _p(att), _p(ybuf), 0, _p(ws), ws.numel(), B, L, Nk,
-                                0, 0, 0, 0, 0.0, 0, 0, 0, 0, 0, int(cross_mode), _p(enc0), _p(enc1), _p(enc_mask0), _p(enc_mask1),
-                                _p(hidden_lp), _p(ylp), _p(kv_pre[0]), _p(kv_pre[1]), _p(kv_index), kv_ld, ctypes.byref(k_out),
-                                ctypes.byref(k_used), _stream()), "madtp_bert_layer")
-    return ybuf, None, None, ylp
+    _check(load().madtp_bert_layer(ctypes.byref(wstruct), _p(hidden), _p(mask2d), _p(att), _p(ybuf), _p(mbuf), _p(ws), ws.numel(),
+                                   B, L, Nk, *sargs, _p(idx), _p(idx_sort), int(cross_mode), _p(enc0), _p(enc1), _p(enc_mask0),
+                                   _p(enc_mask1), _p(hidden_lp), _p(ylp), _p(kv_pre[0]), _p(kv_pre[1]), _p(kv_index), kv_ld,
+                                   ctypes.byref(k_out), ctypes.byref(k_used), _stream()), "madtp_bert_layer")
+    if po is None:
+        return ybuf, None, None, ylp
+    k = k_used.value
+    if k > 0:
+        return (_carve(ybuf, B, k + 2, D), (_carve(mbuf, B, k + 2) if mbuf is not None else None),
+                prune_info(k_out.value, *po[:3], _carve(idx, B, k), idx_sort),
+                _carve(ylp, B, k + 2, ylp.shape[-1]) if ylp is not None else None)
+    return ybuf, None, prune_info(k_out.value, *po[:3]), ylp
 
 
 def vit_block_attn(wstruct, x, token_attn, temperature):
     """x f32 [B,N,D] contiguous -> (x_attn, (score, thr, count, kmax) or None)."""
     B, N, D = x.shape
-    lib = load()
-    nbytes = lib.madtp_vit_block_workspace(B, N, wstruct.dim, wstruct.fc1.n, wstruct.heads, wstruct.dtype)
-    ws = workspace(nbytes, x.device)
+    ws = _vit_ws(wstruct, B, N, x.device)
     out = torch.empty_like(x)
-    if temperature > 0:
-        tp, ldr, ldb, K = _ta_view(token_attn)
-        po = prune_outputs(B, N - 1, x.device)
-        _check(lib.madtp_vit_block_attn(ctypes.byref(wstruct), _p(x), _p(out), _p(ws), ws.numel(), B, N, tp, ldr, ldb, K,
-                                        float(temperature), _p(po[0]), _p(po[1]), _p(po[2]), _p(po[3]), _stream()),
-               "madtp_vit_block_attn")
-        return out, po
-    _check(lib.madtp_vit_block_attn(ctypes.byref(wstruct), _p(x), _p(out), _p(ws), ws.numel(), B, N, 0, 0, 0, 0, 0.0, 0, 0,
-                                    0, 0, _stream()), "madtp_vit_block_attn")
-    return out, None
+    sargs, po = _score_args(token_attn, temperature, B, N - 1, x.device)
+    _check(load().madtp_vit_block_attn(ctypes.byref(wstruct), _p(x), _p(out), _p(ws), ws.numel(), B, N, *sargs, _p(po and po[3]),
+                                       _stream()), "madtp_vit_block_attn")
+    return out, po
 
 
 def vit_block_mlp(wstruct, x, k, score):
     B, N, D = x.shape
-    lib = load()
-    nbytes = lib.madtp_vit_block_workspace(B, N, wstruct.dim, wstruct.fc1.n, wstruct.heads, wstruct.dtype)
-    ws = workspace(nbytes, x.device)
+    ws = _vit_ws(wstruct, B, N, x.device)
     if k > 0:
         y = torch.empty((B, k + 2, D), device=x.device, dtype=torch.float32)
         indices = torch.empty((B, k), device=x.device, dtype=torch.int64)
@@ -978,7 +823,7 @@ def vit_block_mlp(wstruct, x, k, score):
     else:
         y = torch.empty_like(x)
         indices = indices_sort = None
-    _check(lib.madtp_vit_block_mlp(ctypes.byref(wstruct), _p(x), _p(y), _p(ws), ws.numel(), B, N, k, _p(score), _p(indices),
+    _check(load().madtp_vit_block_mlp(ctypes.byref(wstruct), _p(x), _p(y), _p(ws), ws.numel(), B, N, k, _p(score), _p(indices),
                                    _p(indices_sort), _stream()), "madtp_vit_block_mlp")
     return y, indices, indices_sort
 
@@ -1015,27 +860,17 @@ def bert_layer_attn(wstruct, hidden, mask2d, token_attn, temperature, Nk):
     """First half of a BERT layer (madtp_bert_layer_attn: self-attention + output LayerNorm + importance score) for callers with
     their own pruning rule -> (attention_output, (score, threshold, count, kmax) or None)."""
     B, L, D = hidden.shape
-    lib = load()
-    nbytes = lib.madtp_bert_layer_workspace(B, L, Nk, wstruct.dim, wstruct.inter.n, wstruct.heads, wstruct.dtype)
-    ws = workspace(nbytes, hidden.device)
+    ws = _bert_ws(wstruct, B, L, Nk, hidden.device)
     att = torch.empty_like(hidden)
-    if temperature > 0:
-        tp, ldr, ldb, K = _ta_view(token_attn)
-        po = prune_outputs(B, L - 1, hidden.device)
-        _check(lib.madtp_bert_layer_attn(ctypes.byref(wstruct), _p(hidden), _p(mask2d), _p(att), _p(ws), ws.numel(), B, L, Nk,
-                                         tp, ldr, ldb, K, float(temperature), _p(po[0]), _p(po[1]), _p(po[2]), _p(po[3]),
-                                         _stream()), "madtp_bert_layer_attn")
-        return att, po
-    _check(lib.madtp_bert_layer_attn(ctypes.byref(wstruct), _p(hidden), _p(mask2d), _p(att), _p(ws), ws.numel(), B, L, Nk, 0,
-                                     0, 0, 0, 0.0, 0, 0, 0, 0, _stream()), "madtp_bert_layer_attn")
-    return att, None
+    sargs, po = _score_args(token_attn, temperature, B, L - 1, hidden.device)
+    _check(load().madtp_bert_layer_attn(ctypes.byref(wstruct), _p(hidden), _p(mask2d), _p(att), _p(ws), ws.numel(), B, L, Nk, *sargs,
+                                        _p(po and po[3]), _stream()), "madtp_bert_layer_attn")
+    return att, po
 
 
 def bert_layer_rest(wstruct, att, mask2d, k, score, cross_mode, enc0, enc1, Nk, enc_mask0, enc_mask1):
     B, L, D = att.shape
-    lib = load()
-    nbytes = lib.madtp_bert_layer_workspace(B, L, Nk, wstruct.dim, wstruct.inter.n, wstruct.heads, wstruct.dtype)
-    ws = workspace(nbytes, att.device)
+    ws = _bert_ws(wstruct, B, L, Nk, att.device)
     Lp = k + 2 if k > 0 else L
     y = torch.empty((B, Lp, D), device=att.device, dtype=torch.float32)
     indices = indices_sort = mask_out = None
@@ -1044,7 +879,7 @@ def bert_layer_rest(wstruct, att, mask2d, k, score, cross_mode, enc0, enc1, Nk, 
         indices_sort = torch.empty((B, L - 1), device=att.device, dtype=torch.int64)
         if mask2d is not None:
             mask_out = torch.empty((B, Lp), device=att.device, dtype=torch.float32)
-    _check(lib.madtp_bert_layer_rest(ctypes.byref(wstruct), _p(att), _p(mask2d), _p(y), _p(mask_out), _p(ws), ws.numel(), B, L,
+    _check(load().madtp_bert_layer_rest(ctypes.byref(wstruct), _p(att), _p(mask2d), _p(y), _p(mask_out), _p(ws), ws.numel(), B, L,
                                      k, _p(score), _p(indices), _p(indices_sort), int(cross_mode), _p(enc0), _p(enc1), Nk,
                                      _p(enc_mask0), _p(enc_mask1), _stream()), "madtp_bert_layer_rest")
     return y, mask_out, indices, indices_sort
@@ -1243,10 +1078,7 @@ def _io_dtype():
     global _IO_NP
     if _IO_NP is None:
         import numpy as np
-        names = [f[0] for f in LayerIO._fields_]
-        fmts = ["u8"] * 10 + ["i4"] * 3
-        offs = [getattr(LayerIO, n).offset for n in names]
-        _IO_NP = np.dtype({"names": names, "formats": fmts, "offsets": offs, "itemsize": ctypes.sizeof(LayerIO)})
+        _IO_NP = np.dtype(LayerIO)  # numpy reads the ctypes fields: pointers as uintp, ints as int32, the struct's offsets and size
     return _IO_NP
 
 
@@ -1333,14 +1165,10 @@ class EncoderRun:
         k, k_used, n = k_out[layer], k_used_l[layer], self.n_in(layer) - 1
 
         def fill():
-            d = {"k": k, "score": self.view(layer, "score", torch.float32, self.B, n),
-                 "threshold": self.view(layer, "threshold", torch.float32, self.B),
-                 "count": self.view(layer, "count", torch.int32, self.B), "pruned": k_used > 0, "indices": None,
-                 "indices_sort": None}
-            if k_used > 0:
-                d["indices"] = self.view(layer, "indices", torch.int64, self.B, k_used)
-                d["indices_sort"] = self.view(layer, "indices_sort", torch.int64, self.B, n)
-            return d
+            idx = () if k_used <= 0 else (self.view(layer, "indices", torch.int64, self.B, k_used),
+                                          self.view(layer, "indices_sort", torch.int64, self.B, n))
+            return prune_info(k, self.view(layer, "score", torch.float32, self.B, n), self.view(layer, "threshold", torch.float32, self.B),
+                              self.view(layer, "count", torch.int32, self.B), *idx)
         return LazyPruneInfo(fill)
 
     def output(self, layer):
@@ -1364,9 +1192,7 @@ def vit_encoder(weights, x, qargs, temperature, sync_free=False, enqueue_only=Fa
     lib = load()
     wstructs, arr = weights
     L = len(wstructs)
-    w0 = wstructs[0]
-    nbytes = lib.madtp_vit_block_workspace(B, N, w0.dim, w0.fc1.n, w0.heads, w0.dtype)
-    ws = workspace(nbytes, x.device)
+    ws = _vit_ws(wstructs[0], B, N, x.device)
     prune = qargs is not None and temperature > 0
     run = EncoderRun(L, B, N, D, x.device, qargs is not None, prune, False, None)
     q = _query_w(qargs)
@@ -1404,9 +1230,7 @@ def bert_decode_step(weights, x, kv_cache, t, kv_pre, kv_index, kv_ld, Nk, group
     wstructs, arr = weights
     L = len(wstructs)
     w0 = wstructs[0]
-    nbytes = max(lib.madtp_bert_layer_workspace(rows, 1, Nk, w0.dim, w0.inter.n, w0.heads, w0.dtype),
-                 lib.madtp_bert_layer_workspace(rows // group, group, Nk, w0.dim, w0.inter.n, w0.heads, w0.dtype))
-    ws = workspace(nbytes, x.device)
+    ws = workspace(max(_bert_ws_bytes(w0, rows, 1, Nk), _bert_ws_bytes(w0, rows // group, group, Nk)), x.device)
     y = torch.empty_like(x)
     kv = (c_void_p * L)(*[_p(tn) for tn in kv_pre])
     if kv_index.numel() != rows // group:
@@ -1438,8 +1262,7 @@ def bert_encoder(weights, hidden, hidden_lp, mask2d, qargs, temperature, cross_m
     wstructs, arr = weights
     L = len(wstructs)
     w0 = wstructs[0]
-    nbytes = lib.madtp_bert_layer_workspace(B, Lq, Nk, w0.dim, w0.inter.n, w0.heads, w0.dtype)
-    ws = workspace(nbytes, hidden.device)
+    ws = _bert_ws(w0, B, Lq, Nk, hidden.device)
     prune = qargs is not None and temperature > 0
     lp_dtype = None if w0.dtype == F32 else (torch.float16 if w0.dtype == F16S else torch.bfloat16)
     run = EncoderRun(L, B, Lq, D, hidden.device, qargs is not None, prune, mask2d is not None and prune, lp_dtype)

@@ -175,13 +175,11 @@ class Block(nn.Module):
         n = N - 1
         score, thr, count, kmax = hip.token_score(self.attn.score_side, token_attn, temperature, B, self.attn.num_heads, N)
         k = int(kmax.item())  # topk_num = max_b count: one host sync per layer, as vit.py:145
-        info = {"k": k, "score": score, "threshold": thr, "count": count, "pruned": False, "indices": None,
-                "indices_sort": None}
-        self.last_prune = info
+        self.last_prune = hip.prune_info(k, score, thr, count)
         if k < 1 or (n - k) <= 1:  # vit.py:148-149
             return x
         indices, indices_sort, dst_pos, merge_w = hip.token_select(score, k)
-        info.update(pruned=True, indices=indices, indices_sort=indices_sort)
+        self.last_prune = hip.prune_info(k, score, thr, count, indices, indices_sort)
         return hip.token_gather(x, dst_pos, merge_w, k)
 
     def _apply(self, fn, recurse=True):
