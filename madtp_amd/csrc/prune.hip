@@ -14,6 +14,7 @@
 #include <atomic>
 #include <chrono>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #ifndef TRY
@@ -45,20 +46,237 @@ __device__ __forceinline__ float block_max_f(float v, float* red, int tid, int n
 }
 
 // ------------------------------------------------------------------------------------------------ token_score
-// one 512-thread workgroup per sample.  The sample's logits token_attn[b] (n x K f32, <= 150 KB) are staged in LDS
-// once with coalesced float4 loads (STAGED; falls back to reading global memory for very long sequences), then
-//   phase A: per-token terms (row max of the logits, column mass of head-max attention, CLS attention);
-//   phase B: per-dictionary-column softmax over tokens (4 token slices x 128 columns) and
-//            threshold = min_k sum_t softmax_t(x/T)[t,k] * I[t]; survivor count; optional batch max (atomicMax).
+// The pruning decision of a layer (vit.py:125-145), per sample of n = N - 1 patch tokens and K <= 128 dictionary columns:
+//   phase A: per-token terms - tw = row maximum of the logits (vit.py:131), a = column mass of head-max attention (vit.py:126-127),
+//            c = head-diversity weighted CLS attention (vit.py:96-101) - and the score I = (a / sum a + tw / sum tw + c) / 3;
+//   phase B: per dictionary column the softmax over tokens of logits / T; threshold = min_k sum_t softmax[t, k] I[t];
+//   epilogue: survivor count, batch maximum k = max_b count and its hand-over to the host (or to the device-side layer record).
+// Two kernels, 512 threads each, share ONE device function per phase and differ in where the logits sit:
+//   token_score_kernel        one workgroup per sample; the sample's logits [n][K] staged in LDS (STAGED, <= 140 KB), read from
+//                             global memory otherwise;
+//   token_score_split_kernel  G workgroups per sample, each with 128 / G columns [n][128 / G] in LDS (long sequences, small batches).
+// Every sum has a fixed order (row tiles, heads, token slices in index order), so the kernels agree bit for bit wherever their
+// arithmetic is the same, and results do not depend on workgroup placement.
 #ifdef MADTP_TS_TIMING
-__device__ long long g_ts_dbg[16];
+__device__ long long g_ts_dbg[16];  // phase timestamps of workgroup 0 (tools/token_score_phases.py)
 #define TS_MARK(i) do { if (threadIdx.x == 0 && blockIdx.x == 0) g_ts_dbg[i] = wall_clock64(); } while (0)
 #else
 #define TS_MARK(i)
 #endif
-// FAST (fast precision modes only, madtp_set_score_fast): phase B in log2 units with v_exp_f32 and one reciprocal per column
-// instead of two IEEE divisions and a precise expf per logit - phase B is VALU-bound (10 of 17 us at 197 tokens) and the parity
-// modes' arithmetic (FAST = false) has to stay what the reference computes.
+
+constexpr int TS_HMAX = 16;  // heads whose operands a thread holds in registers (more heads: ts_heads_generic)
+
+// ---- phase A, attention-side terms of a thread's two tokens tt[u] (tid and tid + 512, CLAMPED to the last token: straight-line
+// loads without predicates, the surplus lanes' values are never used).  Loads and sums are separate functions so that a caller can
+// request the operands long before it adds them up.  Orders: row tiles 0..nrt-1, then heads 0..H-1 for hs, then heads 0..H-1 for c.
+template <int RB>  // row tiles r0 .. r0 + RB - 1 of the column-mass partials (indices past nrt - 1 re-read the last tile)
+__device__ __forceinline__ void ts_colsum_load(float (&cs)[2][RB], const float* __restrict__ colsum, int b, int nrt, int N,
+                                               const int (&tt)[2], int r0) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int r = 0; r < RB; ++r) cs[u][r] = colsum[((size_t)b * nrt + min(r0 + r, nrt - 1)) * N + tt[u] + 1];
+}
+template <int RB>
+__device__ __forceinline__ void ts_colsum_add(float (&a)[2], const float (&cs)[2][RB], int nrt, int r0) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int r = 0; r < RB; ++r) if (r0 + r < nrt) a[u] += cs[u][r];
+}
+// H <= TS_HMAX: context norms and CLS attention of every head in registers
+__device__ __forceinline__ void ts_heads_load(float (&on)[2][TS_HMAX], float (&pz)[2][TS_HMAX], const float* __restrict__ p0,
+                                              const float* __restrict__ onorm, int b, int H, int N, const int (&tt)[2]) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int h = 0; h < TS_HMAX; ++h) {
+            const size_t o = ((size_t)b * H + min(h, H - 1)) * N + tt[u] + 1;
+            on[u][h] = onorm[o];
+            pz[u][h] = p0[o];
+        }
+}
+__device__ __forceinline__ void ts_heads_reduce(float (&c)[2], const float (&on)[2][TS_HMAX], const float (&pz)[2][TS_HMAX], int H) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        float hs = 0.f, cc = 0.f;
+#pragma unroll
+        for (int h = 0; h < TS_HMAX; ++h) if (h < H) hs += on[u][h];
+#pragma unroll
+        for (int h = 0; h < TS_HMAX; ++h) if (h < H) cc += pz[u][h] * (on[u][h] / (hs + 1e-8f));
+        c[u] = cc;
+    }
+}
+// any head count: the same sums in the same order, operands read where they are used
+__device__ __forceinline__ void ts_heads_generic(float (&c)[2], const float* __restrict__ p0, const float* __restrict__ onorm, int b,
+                                                 int H, int N, const int (&tt)[2]) {
+    for (int u = 0; u < 2; ++u) {
+        float hs = 0.f, cc = 0.f;
+        for (int h = 0; h < H; ++h) hs += onorm[((size_t)b * H + h) * N + tt[u] + 1];
+        for (int h = 0; h < H; ++h) {
+            const size_t o = ((size_t)b * H + h) * N + tt[u] + 1;
+            cc += p0[o] * (onorm[o] / (hs + 1e-8f));
+        }
+        c[u] = cc;
+    }
+}
+// a of both tokens over any number of row tiles (long sequences: nrt = 38..57), loaded where it is used: every load of a batch of RB
+// row tiles is requested before the first add.
+template <int RB>
+__device__ __forceinline__ void ts_colsum_batched(float (&a)[2], const float* __restrict__ colsum, int b, int nrt, int N,
+                                                  const int (&tt)[2]) {
+    for (int r0 = 0; r0 < nrt; r0 += RB) {
+        float cs[2][RB];
+        ts_colsum_load<RB>(cs, colsum, b, nrt, N, tt, r0);
+        ts_colsum_add<RB>(a, cs, nrt, r0);
+    }
+}
+
+// ---- phase A, score: I[t] = (a / sum a + tw / sum tw + c) / 3 (vit.py:134) into I_s and, where score_b is given, to global
+// memory.  tw_s holds the row maxima; the sums over the sample run in thread order (block_sum).
+__device__ __forceinline__ void ts_score_store(const float (&a)[2], const float (&c)[2], const float* tw_s, float* I_s,
+                                               float* __restrict__ score_b, int n, float* red, int tid) {
+    float suma_l = 0.f, sumt_l = 0.f;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int t = tid + u * 512;
+        if (t < n) { suma_l += a[u]; sumt_l += tw_s[t]; }
+    }
+    const float suma = block_sum(suma_l, red, tid, 8);
+    const float sumt = block_sum(sumt_l, red, tid, 8);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        const int t = tid + u * 512;
+        if (t < n) {
+            const float aw = a[u] / (suma + 1e-8f);
+            const float tw = tw_s[t] / (sumt + 1e-8f);
+            const float sc = (aw + tw + c[u]) / 3.0f;
+            I_s[t] = sc;
+            if (score_b) score_b[t] = sc;
+        }
+    }
+    __syncthreads();
+}
+
+// ---- phase B, the reference's arithmetic (vit.py:137-139): three passes over the tokens of a column - x / T and its maximum,
+// expf(x / T - max) and its sum, (e / sum) * I and its sum - each operation rounded on its own.  KC columns per workgroup, S = 512 / KC
+// token slices per column; thread (slice, cl) walks tokens [n slice / S, n (slice + 1) / S) of column cl and the S partials of a
+// column are combined in slice order.  colstat[cl] = sum_t softmax[t, cl] I[t], +inf for a column past K.
+// IN_LDS: x = the column in LDS (element t at x[t * pitch]), private to this thread from here on, so x / T and then e overwrite it in
+// place instead of being recomputed by the next pass (the same values either way).  Otherwise x is the column in global memory.
+template <int KC, int S, bool IN_LDS, class X>
+__device__ __forceinline__ void ts_phase_b_exact(X x, int pitch, bool cval, int cl, int slice, int n, float temperature,
+                                                 const float* I_s, float (*colred)[KC], float* colstat, int tid) {
+    const int t0 = (n * slice) / S, t1 = (n * (slice + 1)) / S;
+    auto at = [&](int t) -> decltype(*x)& {
+        if constexpr (IN_LDS) return x[t * pitch];
+        else return x[(size_t)t * pitch];
+    };
+    float m = -INFINITY;
+    if (cval) {
+#pragma unroll 8
+        for (int t = t0; t < t1; ++t) {
+            const float v = at(t) / temperature;
+            if constexpr (IN_LDS) at(t) = v;
+            m = fmaxf(m, v);
+        }
+    }
+    colred[slice][cl] = m;
+    __syncthreads();
+    m = colred[0][cl];
+#pragma unroll
+    for (int s = 1; s < S; ++s) m = fmaxf(m, colred[s][cl]);
+    __syncthreads();
+    float se = 0.f;
+    if (cval) {
+#pragma unroll 8
+        for (int t = t0; t < t1; ++t) {
+            float e;
+            if constexpr (IN_LDS) { e = expf(at(t) - m); at(t) = e; }
+            else e = expf(at(t) / temperature - m);
+            se += e;
+        }
+    }
+    colred[slice][cl] = se;
+    __syncthreads();
+    float sum = colred[0][cl];
+#pragma unroll
+    for (int s = 1; s < S; ++s) sum += colred[s][cl];
+    __syncthreads();
+    float sw = 0.f;
+    if (cval) {
+#pragma unroll 8
+        for (int t = t0; t < t1; ++t) {
+            float e;
+            if constexpr (IN_LDS) e = at(t);
+            else e = expf(at(t) / temperature - m);
+            sw += (e / sum) * I_s[t];
+        }
+    }
+    colred[slice][cl] = sw;
+    __syncthreads();
+    if (tid < KC) {  // (slice 0: cl == tid)
+        float v = colred[0][tid];
+#pragma unroll
+        for (int s = 1; s < S; ++s) v += colred[s][tid];
+        colstat[tid] = cval ? v : INFINITY;
+    }
+    __syncthreads();
+}
+
+// ---- epilogue: with the sample's threshold thr in every thread - survivors (vit.py:143-145), the per-sample results, the optional
+// device-side batch maximum (kmax), and, when done_ctr is given, the launch-wide ticket: the workgroup that finishes the LAST of the
+// nsamp samples takes k = max_b count and hands it on -
+//   dims_l:    the layer's decision stays on the device (sync-free encoder path): k, the k applied under the BLIP rule (vit.py:148-149:
+//              no pruning when k < 1 or N - 1 - k <= 1) and the next layer's token count; later kernels of the stream read them;
+//   host_slot: straight to host-visible pinned memory, slot[0] = k, then slot[1] = sequence number with system-scope release - the
+//              host spins on the sequence number instead of paying a device-to-host copy plus a stream synchronisation for the one
+//              value it needs per layer (vit.py:145 `.item()`).
+__device__ __forceinline__ void ts_finish(float thr, const float* I_s, int n, int N, int b, int nsamp, float* __restrict__ threshold,
+                                          int32_t* __restrict__ count, int32_t* __restrict__ kmax, int32_t* done_ctr,
+                                          int32_t* host_slot, int seq, int32_t* dims_l, float* red, int tid) {
+    __shared__ int last_s;
+    int cnt = 0;
+    for (int t = tid; t < n; t += 512) cnt += I_s[t] > thr ? 1 : 0;
+    const float total = block_sum((float)cnt, red, tid, 8);  // exact: counts <= 1024
+    if (tid == 0) {
+        threshold[b] = thr;
+        count[b] = (int)total;
+        if (kmax) atomicMax(kmax, (int)total);
+        int last = 0;
+        if (done_ctr) {
+            __threadfence();  // count[b] is visible before the ticket
+            last = atomicAdd(done_ctr, 1) == nsamp - 1;
+        }
+        last_s = last;
+    }
+    if (!done_ctr) return;
+    __syncthreads();
+    if (!last_s) return;
+    int mloc = 0;
+    for (int i = tid; i < nsamp; i += 512) mloc = max(mloc, __hip_atomic_load(count + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    const int kk = (int)block_max_f((float)mloc, red, tid, 8);  // exact: counts <= 1024
+    if (tid == 0) {
+        *done_ctr = 0;  // the ticket is armed again for the next launch
+        if (dims_l) {
+            const int k_used = (kk < 1 || (N - 1 - kk) <= 1) ? 0 : kk;
+            dims_l[1] = kk;
+            dims_l[2] = k_used;
+            dims_l[3] = k_used ? k_used + 2 : N;
+            dims_l[DIMS_STRIDE] = k_used ? k_used + 2 : N;
+        }
+        if (host_slot) {
+            __hip_atomic_store(host_slot, kk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(host_slot + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// One workgroup per sample.  STAGED: the sample's logits token_attn[b] (n x K f32) are copied to LDS once with coalesced float4
+// loads; otherwise every pass reads them from global memory.
+// FAST (fast precision modes only, madtp_set_score_fast; STAGED only): phase B in TWO passes over the staged column and no stores -
+// the maximum of the raw logits (a positive scale commutes with max), then exp2(fma(x, c2, -c2 max)) with c2 = log2(e) / T, its sum and
+// its I-weighted sum together, one reciprocal per column.  Phase B is VALU-bound; the parity modes keep the reference's arithmetic.
 template <bool STAGED, bool FAST = false>
 __global__ __launch_bounds__(512) void token_score_kernel(const float* __restrict__ colsum, int nrt,
                                                           const float* __restrict__ p0, const float* __restrict__ onorm,
@@ -67,13 +285,13 @@ __global__ __launch_bounds__(512) void token_score_kernel(const float* __restric
                                                           int32_t* __restrict__ count, int32_t* __restrict__ kmax, int H,
                                                           int N, int32_t* done_ctr, int32_t* host_slot, int seq,
                                                           int32_t* dims_l = nullptr) {
+    static_assert(STAGED || !FAST, "the fast score arithmetic exists for the staged kernel only");
     if (dims_l) {  // sync-free encoder path: the token count comes from the device-side record of this layer (common.h DevN)
         N = dims_l[0];
         nrt = (N + 15) / 16;
         ldb = N * ldt_g;  // token_attn = rows 1.. of each sample of a dense [B * N, ldt] logits buffer
     }
     __shared__ float I_s[MAXN];
-    __shared__ int last_s;
     __shared__ float tw_s[MAXN];
     __shared__ float red[8];
     __shared__ float colred[4][128];
@@ -82,27 +300,16 @@ __global__ __launch_bounds__(512) void token_score_kernel(const float* __restric
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x, n = N - 1;
     const float* ta_g = ta + (size_t)b * ldb;  // row t <-> patch token t
+    const int tt[2] = {min(tid, n - 1), min(tid + 512, n - 1)};
     TS_MARK(0);
-    // The attention-side operands of this thread's tokens (column-mass partials, CLS attention, context norms: <= 48 values per
-    // token) are requested BEFORE the logits are staged, so that their latency runs under the staging loads instead of after the
-    // row maxima (short sequences; the long-sequence form below loads in batches where it uses them).
-    constexpr int HMAX = 16, RMAX = 16;
-    const bool pre = H <= HMAX && nrt <= RMAX;
-    float on_pre[2][HMAX], pz_pre[2][HMAX], cs_pre[2][RMAX];
-    if (pre) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int t = min(tid + u * 512, n - 1);  // clamped: straight-line loads, the surplus lanes' values are never used
-#pragma unroll
-            for (int h = 0; h < HMAX; ++h) {
-                const size_t o = ((size_t)b * H + min(h, H - 1)) * N + t + 1;
-                on_pre[u][h] = onorm[o];
-                pz_pre[u][h] = p0[o];
-            }
-#pragma unroll
-            for (int r = 0; r < RMAX; ++r) cs_pre[u][r] = colsum[((size_t)b * nrt + min(r, nrt - 1)) * N + t + 1];
-        }
-    }
+    // The attention-side operands that fit the registers (<= 16 row tiles, <= 16 heads: <= 48 values per token) are requested BEFORE
+    // the logits are staged, so that their latency runs under the staging loads and the row maxima instead of after them.  More
+    // row tiles (long sequences) are summed in batches, more heads one by one, where they are used.
+    constexpr int RB = 16;
+    const bool pre_cs = nrt <= RB, pre_h = H <= TS_HMAX;
+    float cs_pre[2][RB], on_pre[2][TS_HMAX], pz_pre[2][TS_HMAX];
+    if (pre_cs) ts_colsum_load<RB>(cs_pre, colsum, b, nrt, N, tt, 0);
+    if (pre_h) ts_heads_load(on_pre, pz_pre, p0, onorm, b, H, N, tt);
     if constexpr (STAGED) {
         const int k4 = K >> 2;  // K % 4 == 0 on this path
         for (int idx = tid; idx < n * k4; idx += 512) {
@@ -112,13 +319,10 @@ __global__ __launch_bounds__(512) void token_score_kernel(const float* __restric
         __syncthreads();
     }
     TS_MARK(1);
-    const int ldt = STAGED ? K : ldt_g;
-    auto TA = [&](int t, int c) -> float { return STAGED ? ta_s[t * ldt + c] : ta_g[(size_t)t * ldt + c]; };
-
-    // token_attn_w = max over dictionary columns (vit.py:131)
+    // row maxima
     if constexpr (STAGED) {
         // four lanes per row, float4 reads, two quad shuffles: 128 rows per pass (a wave-wide reduction per row costs six
-        // dependent cross-lane steps - it was a third of the kernel)
+        // dependent cross-lane steps)
         const int k4 = K >> 2, q = tid & 3;
         for (int t = tid >> 2; t < n; t += 128) {
             float m = -INFINITY;
@@ -133,94 +337,28 @@ __global__ __launch_bounds__(512) void token_score_kernel(const float* __restric
     } else {
         for (int t = wave; t < n; t += 8) {
             float m = -INFINITY;
-            for (int k = lane; k < K; k += 64) m = fmaxf(m, TA(t, k));
+            for (int k = lane; k < K; k += 64) m = fmaxf(m, ta_g[(size_t)t * ldt_g + k]);
             m = wave_max(m);
             if (lane == 0) tw_s[t] = m;
         }
     }
     __syncthreads();
-
     TS_MARK(2);
-    // a = column mass of head-max attention (vit.py:126-127), c = head-diversity weighted CLS attention (vit.py:96-101)
-    // All global operands of a token are requested before any is used (fully unrolled, predicated loads: the head and
-    // row-tile counts are small): one memory latency instead of one per group of four.
-    float a_loc[2], c_loc[2], suma_l = 0.f, sumt_l = 0.f;
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int t = tid + u * 512;
-        a_loc[u] = 0.f; c_loc[u] = 0.f;
-        if (t < n) {
-            float a = 0.f, hs = 0.f, c = 0.f;
-            if (pre) {  // (the same sums in the same order as before the loads moved up)
-#pragma unroll
-                for (int r = 0; r < RMAX; ++r) if (r < nrt) a += cs_pre[u][r];
-#pragma unroll
-                for (int h = 0; h < HMAX; ++h) if (h < H) hs += on_pre[u][h];
-#pragma unroll
-                for (int h = 0; h < HMAX; ++h) if (h < H) c += pz_pre[u][h] * (on_pre[u][h] / (hs + 1e-8f));
-            } else {
-                // long sequences (nrt = 38..57 row tiles at 605..901 tokens): the same sums in the same order, with the loads of
-                // sixteen row tiles requested before the first add (one load per dependent add was ~60 L2 round trips per token)
-                for (int r0 = 0; r0 < nrt; r0 += RMAX) {
-                    float cs[RMAX];
-#pragma unroll
-                    for (int r = 0; r < RMAX; ++r) cs[r] = r0 + r < nrt ? colsum[((size_t)b * nrt + r0 + r) * N + t + 1] : 0.f;
-#pragma unroll
-                    for (int r = 0; r < RMAX; ++r) if (r0 + r < nrt) a += cs[r];
-                }
-                if (H <= HMAX) {
-                    float on[HMAX], pz[HMAX];
-#pragma unroll
-                    for (int h = 0; h < HMAX; ++h) {
-                        const size_t o = ((size_t)b * H + h) * N + t + 1;
-                        on[h] = h < H ? onorm[o] : 0.f;
-                        pz[h] = h < H ? p0[o] : 0.f;
-                    }
-#pragma unroll
-                    for (int h = 0; h < HMAX; ++h) if (h < H) hs += on[h];
-#pragma unroll
-                    for (int h = 0; h < HMAX; ++h) if (h < H) c += pz[h] * (on[h] / (hs + 1e-8f));
-                } else {
-                    for (int h = 0; h < H; ++h) hs += onorm[((size_t)b * H + h) * N + t + 1];
-                    for (int h = 0; h < H; ++h) {
-                        const size_t o = ((size_t)b * H + h) * N + t + 1;
-                        c += p0[o] * (onorm[o] / (hs + 1e-8f));
-                    }
-                }
-            }
-            a_loc[u] = a; c_loc[u] = c;
-            suma_l += a; sumt_l += tw_s[t];
-        }
-    }
+    float a_loc[2] = {0.f, 0.f}, c_loc[2];
+    if (pre_cs) ts_colsum_add<RB>(a_loc, cs_pre, nrt, 0);
+    else ts_colsum_batched<RB>(a_loc, colsum, b, nrt, N, tt);
+    if (pre_h) ts_heads_reduce(c_loc, on_pre, pz_pre, H);
+    else ts_heads_generic(c_loc, p0, onorm, b, H, N, tt);
     TS_MARK(3);
-    const float suma = block_sum(suma_l, red, tid, 8);
-    const float sumt = block_sum(sumt_l, red, tid, 8);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int t = tid + u * 512;
-        if (t < n) {
-            const float aw = a_loc[u] / (suma + 1e-8f);
-            const float tw = tw_s[t] / (sumt + 1e-8f);
-            const float sc = (aw + tw + c_loc[u]) / 3.0f;  // vit.py:134
-            I_s[t] = sc;
-            score[(size_t)b * n + t] = sc;
-        }
-    }
-    __syncthreads();
-
+    ts_score_store(a_loc, c_loc, tw_s, I_s, score + (size_t)b * n, n, red, tid);
     TS_MARK(4);
-    // phase B: softmax over tokens of token_attn/T per column (vit.py:137-139), 4 slices x 128 columns
+    // phase B: 4 token slices x 128 columns
     const int col = tid & 127, slice = tid >> 7;
-    const int t0 = (n * slice) / 4, t1 = (n * (slice + 1)) / 4;
     const bool cval = col < K;
-    // (STAGED: the LDS copy is private to this kernel and element [t][col] is only touched by this thread from here on,
-    //  so x/T and then exp(x/T - max) overwrite it in place - the arithmetic of each pass is unchanged, it just is not
-    //  repeated by the next one)
-    float m = -INFINITY;
-    const float c2 = 1.44269504088896341f / temperature;  // FAST: logits in log2 units
-    if constexpr (FAST && STAGED) {
-        // fast modes: TWO passes over the staged column and no stores - the maximum of the raw logits (a positive scale commutes
-        // with max), then exp2(fma(x, c2, -c2 max)), its sum and its I-weighted sum together (sw / sum = the softmax-weighted score)
+    if constexpr (FAST) {
+        const int t0 = (n * slice) / 4, t1 = (n * (slice + 1)) / 4;
+        const float c2 = 1.44269504088896341f / temperature;  // logits in log2 units
+        float m = -INFINITY;
         if (cval) {
 #pragma unroll 8
             for (int t = t0; t < t1; ++t) m = fmaxf(m, ta_s[t * K + col]);
@@ -248,101 +386,28 @@ __global__ __launch_bounds__(512) void token_score_kernel(const float* __restric
             colstat[tid] = cval ? sw * __builtin_amdgcn_rcpf(sum) : INFINITY;
         }
         __syncthreads();
+    } else if constexpr (STAGED) {
+        ts_phase_b_exact<128, 4, true>(ta_s + col, K, cval, col, slice, n, temperature, I_s, colred, colstat, tid);
     } else {
-    if (cval) {
-#pragma unroll 8
-        for (int t = t0; t < t1; ++t) {
-            const float v = TA(t, col) / temperature;
-            if constexpr (STAGED) ta_s[t * K + col] = v;
-            m = fmaxf(m, v);
-        }
-    }
-    colred[slice][col] = m;
-    __syncthreads();
-    m = fmaxf(fmaxf(colred[0][col], colred[1][col]), fmaxf(colred[2][col], colred[3][col]));
-    __syncthreads();
-    float se = 0.f;
-    if (cval) {
-#pragma unroll 8
-        for (int t = t0; t < t1; ++t) {
-            float e;
-            if constexpr (STAGED) { e = expf(ta_s[t * K + col] - m); ta_s[t * K + col] = e; }
-            else e = expf(TA(t, col) / temperature - m);
-            se += e;
-        }
-    }
-    colred[slice][col] = se;
-    __syncthreads();
-    const float sum = ((colred[0][col] + colred[1][col]) + colred[2][col]) + colred[3][col];
-    __syncthreads();
-    float sw = 0.f;
-    if (cval) {
-#pragma unroll 8
-        for (int t = t0; t < t1; ++t) {
-            const float e = STAGED ? ta_s[t * K + col] : expf(TA(t, col) / temperature - m);
-            sw += (e / sum) * I_s[t];
-        }
-    }
-    colred[slice][col] = sw;
-    __syncthreads();
-    if (tid < 128) colstat[tid] = cval ? ((colred[0][col] + colred[1][col]) + colred[2][col]) + colred[3][col] : INFINITY;
-    __syncthreads();
+        ts_phase_b_exact<128, 4, false>(ta_g + col, ldt_g, cval, col, slice, n, temperature, I_s, colred, colstat, tid);
     }
     TS_MARK(5);
     // threshold = min over columns (vit.py:141)
     float thr = INFINITY;
     for (int k = lane; k < 128; k += 64) thr = fminf(thr, colstat[k]);
     thr = wave_min(thr);
-    // survivors (vit.py:143-145)
-    int cnt = 0;
-    for (int t = tid; t < n; t += 512) cnt += I_s[t] > thr ? 1 : 0;
-    const float total = block_sum((float)cnt, red, tid, 8);  // exact: counts <= 1024
     TS_MARK(6);
-    if (tid == 0) {
-        threshold[b] = thr;
-        count[b] = (int)total;
-        if (kmax) atomicMax(kmax, (int)total);
-        int last = 0;
-        if (done_ctr) {
-            __threadfence();  // count[b] is visible before the ticket
-            last = atomicAdd(done_ctr, 1) == (int)gridDim.x - 1;
-        }
-        last_s = last;
-    }
-    if (!done_ctr) return;
-    __syncthreads();
-    if (!last_s) return;
-    // Last workgroup of the launch: k = max_b count goes straight to host-visible pinned memory (slot[0] = k, then
-    // slot[1] = sequence number with system-scope release) - the host spins on the sequence number instead of paying a
-    // device-to-host copy plus a stream synchronisation for the one value it needs per layer (vit.py:145 `.item()`).
-    int mloc = 0;
-    for (int i = tid; i < (int)gridDim.x; i += 512) mloc = max(mloc, __hip_atomic_load(count + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    const int kk = (int)block_max_f((float)mloc, red, tid, 8);  // exact: counts <= 1024
-    if (tid == 0) {
-        *done_ctr = 0;
-        if (dims_l) {
-            // the layer's decision stays on the device: k, the k applied under the BLIP rule (vit.py:148-149: no pruning when
-            // k < 1 or N - 1 - k <= 1) and the next layer's token count; later kernels of the stream read them (kernel boundary)
-            const int k_used = (kk < 1 || (N - 1 - kk) <= 1) ? 0 : kk;
-            dims_l[1] = kk;
-            dims_l[2] = k_used;
-            dims_l[3] = k_used ? k_used + 2 : N;
-            dims_l[DIMS_STRIDE] = k_used ? k_used + 2 : N;
-        }
-        if (host_slot) {
-            __hip_atomic_store(host_slot, kk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(host_slot + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
+    ts_finish(thr, I_s, n, N, b, (int)gridDim.x, threshold, count, kmax, done_ctr, host_slot, seq, dims_l, red, tid);
 }
 
 // Long sequences (the logits of a sample no longer fit the LDS: 577 / 901 tokens at 384^2 / 480^2 images) at small batches: one
-// workgroup per sample leaves most of the chip idle (VQA: 32 samples -> 32 of 256 CUs, 124 us per launch).  Here a sample is
-// split over G workgroups by DICTIONARY COLUMNS: every workgroup repeats the cheap per-token phase A (so it owns the complete
-// score vector I), runs the three softmax-over-tokens passes of phase B for its 128/G columns with 512/(128/G) token slices,
-// and publishes the minimum of its columns' sums; the last workgroup of the sample to arrive (agent-scope ticket) takes the
-// minimum over the G partial minima (exact, order-free), counts the survivors and takes part in the launch-wide ticket that
-// hands k to the host.  tick / part: per-sample scratch of the hand-over slot (zeroed once, every ticket resets itself).
+// workgroup per sample leaves most of the chip idle (VQA: 32 samples -> 32 of 256 CUs).  Here a sample is split over G workgroups
+// by DICTIONARY COLUMNS: every workgroup repeats the cheap phase A (so it owns the complete score vector I), runs phase B for its
+// KC = 128 / G columns with S = 512 / KC token slices and publishes the minimum of its columns' sums; the last workgroup of the sample
+// to arrive (agent-scope ticket) takes the minimum over the G partial minima (exact, order-free) and runs the epilogue.
+// tick / part: per-sample scratch of the hand-over slot (zeroed once, every ticket resets itself).
+// FAST (fast precision modes only): phase B's three passes in log2 units - x * (log2(e) / T), exp2 (v_exp_f32), fma accumulation and
+// one reciprocal per column.  Not the arithmetic of token_score_kernel<true, true>: the two give different bits.
 template <int G, bool FAST = false>
 __global__ __launch_bounds__(512, 2) void token_score_split_kernel(const float* __restrict__ colsum, int nrt,
                                                                 const float* __restrict__ p0, const float* __restrict__ onorm,
@@ -353,30 +418,23 @@ __global__ __launch_bounds__(512, 2) void token_score_split_kernel(const float* 
                                                                 float* part, int nsamp) {
     constexpr int KC = 128 / G, S = 512 / KC;  // columns per workgroup, token slices
     __shared__ float I_s[MAXN];
-    __shared__ int last_s, lastg_s;
+    __shared__ int lastg_s;
     __shared__ float tw_s[MAXN];
     __shared__ float red[8];
     __shared__ float colred[S][KC];
     __shared__ float colstat[KC];
     const int tid = threadIdx.x, lane = tid & 63;
     // The G workgroups of a sample share its logits and attention statistics, so they sit on ONE XCD (workgroup id % 8 is the
-    // XCD: sample b lives on XCD b % 8, its workgroups are that XCD's slots (b / 8) G .. + G - 1).  With the sample's workgroups
-    // dealt round-robin over the XCDs every L2 fetched every sample (8 x 11.5 MB through the fabric at 32 x 901 tokens: the row
-    // max alone ran 17 us at ~5 TB/s of fabric traffic).
+    // XCD: sample b lives on XCD b % 8, its workgroups are that XCD's slots (b / 8) G .. + G - 1).  Dealt round-robin over the XCDs,
+    // every L2 would fetch every sample (8 x 11.5 MB through the fabric at 32 x 901 tokens).
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     const int g = slot % G, b = (slot / G) * 8 + xcd, n = N - 1;
     if (b >= nsamp) return;
     const float* ta_g = ta + (size_t)b * ldb;
-#ifdef MADTP_TS_TIMING
-#define TSS_MARK(i) do { if (threadIdx.x == 0 && blockIdx.x == 0) g_ts_dbg[i] = wall_clock64(); } while (0)
-#else
-#define TSS_MARK(i)
-#endif
-    TSS_MARK(0);
+    TS_MARK(0);
     // this workgroup's KC columns of the sample's logits, staged once ([n][KC] f32: <= 57 KiB at 901 tokens and G = 8) - the three
     // softmax passes of phase B then read LDS instead of walking 64-byte pieces of global rows three times
     extern __shared__ __attribute__((aligned(16))) float cols_s[];
-    auto TA = [&](int t, int c) -> float { return cols_s[t * KC + (c - g * KC)]; };
     {
         constexpr int C4 = KC / 4;
         for (int idx = tid; idx < n * C4; idx += 512) {
@@ -385,14 +443,11 @@ __global__ __launch_bounds__(512, 2) void token_score_split_kernel(const float* 
                 *(float4*)(cols_s + t * KC + c) = *(const float4*)(ta_g + (size_t)t * ldt + g * KC + c);
         }
     }
-
-    TSS_MARK(1);
-    // ---- phase A (identical in every workgroup of the sample): row max of the logits, four lanes per row, float4 reads (all of
-    //      a lane's <= 8 loads of a row are requested before the first max)
+    TS_MARK(1);
+    // ---- phase A (identical in every workgroup of the sample).  Row maxima from global memory: eight lanes per row, four float4
+    // per lane (K <= 128), 64 rows per pass and EIGHT passes requested at once (32 loads per lane in flight: the sample's 360 KB at
+    // 901 tokens are two round trips instead of one per 128 rows).  max is exact and order-free.
     {
-        // eight lanes per row, four float4 per lane (K <= 128), 64 rows per pass and EIGHT passes requested at once (32 loads per
-        // lane in flight: the sample's 360 KB at 901 tokens are two round trips instead of one per 128 rows - the row max was a
-        // third of this kernel).  max is exact and order-free.
         const int k4 = K >> 2, q = tid & 7;  // K % 4 == 0, ldt % 4 == 0, 16-byte aligned rows (launch condition)
         for (int tb = tid >> 3; tb < n; tb += 512) {
             float4 v[8][4];
@@ -420,134 +475,75 @@ __global__ __launch_bounds__(512, 2) void token_score_split_kernel(const float* 
         }
     }
     __syncthreads();
-    TSS_MARK(2);
-    // a = column mass of head-max attention, c = head-diversity weighted CLS attention (as in token_score_kernel: the same sums in
-    // the same order).  Every load of BOTH tokens of a thread is requested before the first add - clamped indices instead of
-    // predicates: straight-line code, no waits at control-flow merges - in batches of 32 row tiles (nrt = 38..57 here).
-    constexpr int HMAX = 16, RB = 32;
-    float a_loc[2] = {0.f, 0.f}, c_loc[2] = {0.f, 0.f}, suma_l = 0.f, sumt_l = 0.f;
+    TS_MARK(2);
     const int tt[2] = {min(tid, n - 1), min(tid + 512, n - 1)};
-    for (int r0 = 0; r0 < nrt; r0 += RB) {
-        float cs[2][RB];
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int r = 0; r < RB; ++r) cs[u][r] = colsum[((size_t)b * nrt + min(r0 + r, nrt - 1)) * N + tt[u] + 1];
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int r = 0; r < RB; ++r) if (r0 + r < nrt) a_loc[u] += cs[u][r];
-    }
-    if (H <= HMAX) {
-        float on[2][HMAX], pz[2][HMAX];
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int h = 0; h < HMAX; ++h) {
-                const size_t o = ((size_t)b * H + min(h, H - 1)) * N + tt[u] + 1;
-                on[u][h] = onorm[o];
-                pz[u][h] = p0[o];
-            }
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            float hs = 0.f, c = 0.f;
-#pragma unroll
-            for (int h = 0; h < HMAX; ++h) if (h < H) hs += on[u][h];
-#pragma unroll
-            for (int h = 0; h < HMAX; ++h) if (h < H) c += pz[u][h] * (on[u][h] / (hs + 1e-8f));
-            c_loc[u] = c;
-        }
+    float a_loc[2] = {0.f, 0.f}, c_loc[2];
+    ts_colsum_batched<32>(a_loc, colsum, b, nrt, N, tt);
+    if (H <= TS_HMAX) {
+        float on[2][TS_HMAX], pz[2][TS_HMAX];
+        ts_heads_load(on, pz, p0, onorm, b, H, N, tt);
+        ts_heads_reduce(c_loc, on, pz, H);
     } else {
-        for (int u = 0; u < 2; ++u) {
-            float hs = 0.f, c = 0.f;
-            for (int h = 0; h < H; ++h) hs += onorm[((size_t)b * H + h) * N + tt[u] + 1];
-            for (int h = 0; h < H; ++h) {
-                const size_t o = ((size_t)b * H + h) * N + tt[u] + 1;
-                c += p0[o] * (onorm[o] / (hs + 1e-8f));
-            }
-            c_loc[u] = c;
-        }
+        ts_heads_generic(c_loc, p0, onorm, b, H, N, tt);
     }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int t = tid + u * 512;
-        if (t < n) { suma_l += a_loc[u]; sumt_l += tw_s[t]; }
-        else { a_loc[u] = 0.f; c_loc[u] = 0.f; }
-    }
-    TSS_MARK(3);
-    const float suma = block_sum(suma_l, red, tid, 8);
-    const float sumt = block_sum(sumt_l, red, tid, 8);
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        const int t = tid + u * 512;
-        if (t < n) {
-            const float aw = a_loc[u] / (suma + 1e-8f);
-            const float tw = tw_s[t] / (sumt + 1e-8f);
-            const float sc = (aw + tw + c_loc[u]) / 3.0f;  // vit.py:134
-            I_s[t] = sc;
-            if (g == 0) score[(size_t)b * n + t] = sc;
-        }
-    }
-    __syncthreads();
-
-    TSS_MARK(4);
-    // ---- phase B on columns [g KC, (g+1) KC): softmax over tokens of token_attn / T (vit.py:137-139), S token slices
+    TS_MARK(3);
+    ts_score_store(a_loc, c_loc, tw_s, I_s, g == 0 ? score + (size_t)b * n : nullptr, n, red, tid);
+    TS_MARK(4);
+    // ---- phase B on columns [g KC, (g + 1) KC)
     const int cl = tid % KC, slice = tid / KC, col = g * KC + cl;
-    const int t0 = (n * slice) / S, t1 = (n * (slice + 1)) / S;
     const bool cval = col < K;
-    // (the LDS copy is private to this workgroup and element [t][col] is only touched by this thread: x / T and then
-    //  exp(x / T - max) overwrite it in place - each pass's arithmetic is unchanged, it just is not repeated by the next)
-    float m = -INFINITY;
-    if (cval) {
+    if constexpr (FAST) {
+        // (as in ts_phase_b_exact, the column in LDS is private to this thread and overwritten in place)
+        const int t0 = (n * slice) / S, t1 = (n * (slice + 1)) / S;
+        float m = -INFINITY;
+        if (cval) {
 #pragma unroll 8
-        for (int t = t0; t < t1; ++t) {
-            const float v = FAST ? TA(t, col) * (1.44269504088896341f / temperature) : TA(t, col) / temperature;  // (FAST: log2 units)
-            cols_s[t * KC + cl] = v;
-            m = fmaxf(m, v);
+            for (int t = t0; t < t1; ++t) {
+                const float v = cols_s[t * KC + cl] * (1.44269504088896341f / temperature);
+                cols_s[t * KC + cl] = v;
+                m = fmaxf(m, v);
+            }
         }
-    }
-    colred[slice][cl] = m;
-    __syncthreads();
-    m = colred[0][cl];
+        colred[slice][cl] = m;
+        __syncthreads();
+        m = colred[0][cl];
 #pragma unroll
-    for (int s2 = 1; s2 < S; ++s2) m = fmaxf(m, colred[s2][cl]);
-    __syncthreads();
-    float se = 0.f;
-    if (cval) {
+        for (int s2 = 1; s2 < S; ++s2) m = fmaxf(m, colred[s2][cl]);
+        __syncthreads();
+        float se = 0.f;
+        if (cval) {
 #pragma unroll 8
-        for (int t = t0; t < t1; ++t) {
-            const float e = FAST ? __builtin_amdgcn_exp2f(cols_s[t * KC + cl] - m) : expf(cols_s[t * KC + cl] - m);
-            cols_s[t * KC + cl] = e;
-            se += e;
+            for (int t = t0; t < t1; ++t) {
+                const float e = __builtin_amdgcn_exp2f(cols_s[t * KC + cl] - m);
+                cols_s[t * KC + cl] = e;
+                se += e;
+            }
         }
-    }
-    colred[slice][cl] = se;
-    __syncthreads();
-    float sum = colred[0][cl];
+        colred[slice][cl] = se;
+        __syncthreads();
+        float sum = colred[0][cl];
 #pragma unroll
-    for (int s2 = 1; s2 < S; ++s2) sum += colred[s2][cl];  // fixed order
-    __syncthreads();
-    float sw = 0.f;
-    if (cval) {
-        if constexpr (FAST) {
+        for (int s2 = 1; s2 < S; ++s2) sum += colred[s2][cl];  // fixed order
+        __syncthreads();
+        float sw = 0.f;
+        if (cval) {
 #pragma unroll 8
             for (int t = t0; t < t1; ++t) sw = fmaf(cols_s[t * KC + cl], I_s[t], sw);
             sw *= __builtin_amdgcn_rcpf(sum);
-        } else {
-#pragma unroll 8
-            for (int t = t0; t < t1; ++t) sw += (cols_s[t * KC + cl] / sum) * I_s[t];
         }
-    }
-    colred[slice][cl] = sw;
-    __syncthreads();
-    if (tid < KC) {
-        float v = colred[0][tid];
+        colred[slice][cl] = sw;
+        __syncthreads();
+        if (tid < KC) {
+            float v = colred[0][tid];
 #pragma unroll
-        for (int s2 = 1; s2 < S; ++s2) v += colred[s2][tid];
-        colstat[tid] = (g * KC + tid) < K ? v : INFINITY;
+            for (int s2 = 1; s2 < S; ++s2) v += colred[s2][tid];
+            colstat[tid] = cval ? v : INFINITY;
+        }
+        __syncthreads();
+    } else {
+        ts_phase_b_exact<KC, S, true>(cols_s + cl, KC, cval, cl, slice, n, temperature, I_s, colred, colstat, tid);
     }
-    __syncthreads();
-    TSS_MARK(5);
+    TS_MARK(5);
     float pm = INFINITY;
     for (int k = lane; k < KC; k += 64) pm = fminf(pm, colstat[k]);
     pm = wave_min(pm);
@@ -559,38 +555,17 @@ __global__ __launch_bounds__(512, 2) void token_score_split_kernel(const float* 
         lastg_s = atomicAdd(tick + b, 1) == G - 1;
     }
     __syncthreads();
-    TSS_MARK(6);
+    TS_MARK(6);
     if (!lastg_s) return;
-    if (tid == 0) __threadfence();
+    if (tid == 0) {
+        __threadfence();
+        tick[b] = 0;  // the scratch is clean again for the next launch on this slot (ordered before the launch-wide ticket)
+    }
     __syncthreads();
     float thr = INFINITY;
 #pragma unroll
     for (int i = 0; i < G; ++i) thr = fminf(thr, __hip_atomic_load(part + (size_t)b * G + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    int cnt = 0;
-    for (int t = tid; t < n; t += 512) cnt += I_s[t] > thr ? 1 : 0;
-    const float total = block_sum((float)cnt, red, tid, 8);  // exact: counts <= 1024
-    if (tid == 0) {
-        tick[b] = 0;  // the scratch is clean again for the next launch on this slot
-        threshold[b] = thr;
-        count[b] = (int)total;
-        int last = 0;
-        if (done_ctr) {
-            __threadfence();
-            last = atomicAdd(done_ctr, 1) == nsamp - 1;
-        }
-        last_s = last;
-    }
-    if (!done_ctr) return;
-    __syncthreads();
-    if (!last_s) return;
-    int mloc = 0;
-    for (int i = tid; i < nsamp; i += 512) mloc = max(mloc, __hip_atomic_load(count + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    const int kk = (int)block_max_f((float)mloc, red, tid, 8);
-    if (tid == 0) {
-        *done_ctr = 0;
-        __hip_atomic_store(host_slot, kk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        __hip_atomic_store(host_slot + 1, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    ts_finish(thr, I_s, n, N, b, nsamp, threshold, count, nullptr, done_ctr, host_slot, seq, nullptr, red, tid);
 }
 
 // ----------------------------------------------------------------------------------------------- token_select
@@ -894,24 +869,22 @@ __global__ __launch_bounds__(256) void vector_gather_kernel(const float* __restr
 }
 
 // ----------------------------------------------------------------------------------------------- query_att_ft
-// grid (dim/256, B); 4 waves, wave w owns output columns [256*bx + 64w, +64) (4 MFMA column tiles) for all K<=112
-// dictionary rows (7 row tiles): C[c, d] = sum_t w[c,t] * ft[t, d] with the exact-f32 MFMA 16x16x4
-// (A = w: row c, k-slot g <-> t = 4*step+g;  B = ft: k-slot g, column d).  The softmax weights of a 128-token chunk
-// are computed ONCE per workgroup into LDS (they used to be re-evaluated by every wave of every column block) so the
-// MFMA loop only issues ds_read_b32 + coalesced 64-byte row-segment loads.
+// Exact-f32 form (parity modes).  grid (dim/256, B); 4 waves, wave w owns output columns [256*bx + 64w, +64) (4 MFMA column tiles)
+// for all K<=112 dictionary rows (7 row tiles): C[c, d] = sum_t w[c,t] * ft[t, d] with the exact-f32 MFMA 16x16x4
+// (A = w: row c, k-slot g <-> t = 4*step+g;  B = ft: k-slot g, column d).
 constexpr int AF_TCHUNK = 128, AF_KP = 112;
-__global__ __launch_bounds__(256) void query_att_ft_kernel(const float* __restrict__ ta, int ldt, int ldb, int K,
-                                                           const float* __restrict__ ft, int ldf, int ldfb,
-                                                           float* __restrict__ out, float inv_sqrt_sd, int accumulate,
-                                                           int n, int dim) {
+
+// One segment (one layer's logits ta_b [n][ldt] and token rows xb [n][ldf] of the sample) added to acc, which the caller zeroes (a
+// helper that zeroes it itself costs the single-segment kernel its second wave per SIMD): the column softmax
+// statistics over tokens (2 token slices x 128 columns: expf, true division), then per 128-token chunk the softmax weights ONCE per
+// workgroup into LDS, so the MFMA loop only issues ds_read_b32 + coalesced 64-byte row-segment loads.  The LDS it uses is its own;
+// a caller that runs it again separates the calls with a barrier.
+__device__ __forceinline__ void att_ft_exact_segment(f32x4 (&acc)[7][4], const float* __restrict__ ta_b, int ldt,
+                                                     const float* __restrict__ xb, int ldf, int n, int K, float inv_sqrt_sd, int d0,
+                                                     int tid, int l16, int g) {
     __shared__ float mx[128], sm[128];
     __shared__ float part[2][128];
     __shared__ float wl[AF_TCHUNK * AF_KP];  // [t][c]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l16 = lane & 15, g = lane >> 4;
-    const int b = blockIdx.y;
-    const float* ta_b = ta + (size_t)b * ldb;
-    // column softmax statistics over tokens: 2 token slices x 128 columns
     {
         const int c = tid & 127, sl = tid >> 7;
         const int t0 = sl ? n / 2 : 0, t1 = sl ? n : n / 2;
@@ -934,13 +907,6 @@ __global__ __launch_bounds__(256) void query_att_ft_kernel(const float* __restri
         if (tid < 128) { mx[tid] = m; sm[tid] = c < K ? part[0][c] + part[1][c] : 1.f; }
         __syncthreads();
     }
-    const int d0 = blockIdx.x * 256 + wave * 64 + l16;
-    f32x4 acc[7][4];
-#pragma unroll
-    for (int mt = 0; mt < 7; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const float* xb = ft + (size_t)b * ldfb;
     for (int tc = 0; tc < n; tc += AF_TCHUNK) {
         const int tn = min(AF_TCHUNK, n - tc);
         const int tn4 = (tn + 3) & ~3;
@@ -966,6 +932,18 @@ __global__ __launch_bounds__(256) void query_att_ft_kernel(const float* __restri
             }
         }
     }
+}
+
+__global__ __launch_bounds__(256) void query_att_ft_kernel(const float* __restrict__ ta, int ldt, int ldb, int K,
+                                                           const float* __restrict__ ft, int ldf, int ldfb,
+                                                           float* __restrict__ out, float inv_sqrt_sd, int accumulate,
+                                                           int n, int dim) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l16 = lane & 15, g = lane >> 4;
+    const int b = blockIdx.y;
+    const int d0 = blockIdx.x * 256 + wave * 64 + l16;
+    f32x4 acc[7][4] = {};
+    att_ft_exact_segment(acc, ta + (size_t)b * ldb, ldt, ft + (size_t)b * ldfb, ldf, n, K, inv_sqrt_sd, d0, tid, l16, g);
 #pragma unroll
     for (int mt = 0; mt < 7; ++mt)
 #pragma unroll
@@ -1007,9 +985,6 @@ struct AttFtSegs { AttFtSeg s[AB_MAXSEG]; int nseg; };
 // [B, K, dim] sum per layer and in one launch (it can run on the auxiliary stream like the fast-mode kernel).
 __global__ __launch_bounds__(256) void query_att_ft_exact_multi_kernel(AttFtSegs segs, int K, float* __restrict__ out,
                                                                        float inv_sqrt_sd, int accumulate, int dim) {
-    __shared__ float mx[128], sm[128];
-    __shared__ float part[2][128];
-    __shared__ float wl[AF_TCHUNK * AF_KP];  // [t][c]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l16 = lane & 15, g = lane >> 4;
     const int b = blockIdx.y;
@@ -1021,62 +996,10 @@ __global__ __launch_bounds__(256) void query_att_ft_exact_multi_kernel(AttFtSegs
         for (int nt = 0; nt < 4; ++nt) tot[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int si = 0; si < segs.nseg; ++si) {
         const AttFtSeg sg = segs.s[si];
-        const int n = sg.n, ldt = sg.ldt, ldf = sg.ldf;
-        const float* ta_b = sg.ta + (size_t)b * sg.ldb;
-        const float* xb = sg.ft + (size_t)b * sg.ldfb;
-        __syncthreads();
-        {
-            const int c = tid & 127, sl = tid >> 7;
-            const int t0 = sl ? n / 2 : 0, t1 = sl ? n : n / 2;
-            float m = -INFINITY;
-            if (c < K) {
-#pragma unroll 8
-                for (int t = t0; t < t1; ++t) m = fmaxf(m, ta_b[(size_t)t * ldt + c] * inv_sqrt_sd);
-            }
-            part[sl][c] = m;
-            __syncthreads();
-            m = fmaxf(part[0][c], part[1][c]);
-            __syncthreads();
-            float s = 0.f;
-            if (c < K) {
-#pragma unroll 8
-                for (int t = t0; t < t1; ++t) s += expf(ta_b[(size_t)t * ldt + c] * inv_sqrt_sd - m);
-            }
-            part[sl][c] = s;
-            __syncthreads();
-            if (tid < 128) { mx[tid] = m; sm[tid] = c < K ? part[0][c] + part[1][c] : 1.f; }
-            __syncthreads();
-        }
-        f32x4 acc[7][4];
-#pragma unroll
-        for (int mt = 0; mt < 7; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int tc = 0; tc < n; tc += AF_TCHUNK) {
-            const int tn = min(AF_TCHUNK, n - tc);
-            const int tn4 = (tn + 3) & ~3;
-            __syncthreads();
-            for (int idx = tid; idx < tn4 * AF_KP; idx += 256) {
-                const int t = idx / AF_KP, c = idx % AF_KP;
-                float w = 0.f;
-                if (t < tn && c < K) w = expf(ta_b[(size_t)(tc + t) * ldt + c] * inv_sqrt_sd - mx[c]) / sm[c];
-                wl[idx] = w;
-            }
-            __syncthreads();
-            for (int t4 = 0; t4 < tn; t4 += 4) {
-                const int t = t4 + g;
-                float xv[4];
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) xv[nt] = t < tn ? xb[(size_t)(tc + t) * ldf + d0 + 16 * nt] : 0.f;
-#pragma unroll
-                for (int mt = 0; mt < 7; ++mt) {
-                    const float w = wl[t * AF_KP + mt * 16 + l16];
-#pragma unroll
-                    for (int nt = 0; nt < 4; ++nt)
-                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, xv[nt], acc[mt][nt], 0, 0, 0);
-                }
-            }
-        }
+        f32x4 acc[7][4] = {};
+        __syncthreads();  // the previous segment's readers of the staging LDS are done
+        att_ft_exact_segment(acc, sg.ta + (size_t)b * sg.ldb, sg.ldt, sg.ft + (size_t)b * sg.ldfb, sg.ldf, sg.n, K, inv_sqrt_sd, d0, tid,
+                             l16, g);
         // running sum in layer order: the first segment of a non-accumulating call initialises it (x + 0 would also be exact,
         // but -0 + 0 is not -0), later ones add - the same roundings as `out = out + att_ft_l` per layer
         const bool first = si == 0 && !accumulate;
@@ -1481,48 +1404,55 @@ static bool split_enabled() {  // MADTP_TS_SPLIT=0: always one workgroup per sam
     return v != 0;
 }
 
+// A runtime flag as a template argument: f(std::true_type{}) or f(std::false_type{}).
+template <class F>
+static int with_flag(bool on, F&& f) { return on ? f(std::true_type{}) : f(std::false_type{}); }
+
+// The one launch of token_score.  dims_l: the device-length entry (the token count is read from the layer's record); it passes no
+// tick / part scratch and so never takes the split kernel.
 static int token_score_launch(const float* colsum_part, int n_row_tiles, const float* p0, const float* onorm,
                               const float* token_attn, int ldt, int ldb, int K, float temperature, float* score,
                               float* threshold, int32_t* count, int32_t* kmax, int B, int H, int N, int32_t* done_ctr,
-                              int32_t* host_slot, int seq, void* stream, int32_t* tick = nullptr, float* part = nullptr) {
+                              int32_t* host_slot, int seq, void* stream, int32_t* tick = nullptr, float* part = nullptr,
+                              int32_t* dims_l = nullptr) {
     if (!colsum_part || !p0 || !onorm || !token_attn || !score || !threshold || !count) return MADTP_E_BADARG;
     if (B <= 0 || H <= 0 || N < 2 || n_row_tiles <= 0 || !(temperature > 0.f)) return MADTP_E_BADARG;
     if (N - 1 > MAXN || K > 128 || K <= 0 || ldt < K) return MADTP_E_SHAPE;
     const size_t stage_bytes = (size_t)(N - 1) * K * sizeof(float);
-    const bool staged = K % 4 == 0 && ldt % 4 == 0 && ldb % 4 == 0 && aligned16(token_attn) && stage_bytes <= 140 * 1024;
+    const bool vec4 = K % 4 == 0 && ldt % 4 == 0 && ldb % 4 == 0 && aligned16(token_attn);  // float4 reads of the logits
+    const bool staged = vec4 && stage_bytes <= 140 * 1024;
+    auto one_workgroup = [&](auto kernel, size_t lds_bytes) {
+        hipLaunchKernelGGL(kernel, dim3(B), dim3(512), lds_bytes, (hipStream_t)stream, colsum_part, n_row_tiles, p0, onorm, token_attn,
+                           ldt, ldb, K, temperature, score, threshold, count, kmax, H, N, done_ctr, host_slot, seq, dims_l);
+    };
+    int rc = 0;
     if (staged) {
-        if (score_fast()) {
-            MADTP_ENSURE_MAX_LDS((token_score_kernel<true, true>), 140 * 1024);
-            hipLaunchKernelGGL((token_score_kernel<true, true>), dim3(B), dim3(512), stage_bytes, (hipStream_t)stream, colsum_part,
-                               n_row_tiles, p0, onorm, token_attn, ldt, ldb, K, temperature, score, threshold, count, kmax, H, N,
-                               done_ctr, host_slot, seq);
-        } else {
-            MADTP_ENSURE_MAX_LDS(token_score_kernel<true>, 140 * 1024);
-            hipLaunchKernelGGL(token_score_kernel<true>, dim3(B), dim3(512), stage_bytes, (hipStream_t)stream, colsum_part,
-                               n_row_tiles, p0, onorm, token_attn, ldt, ldb, K, temperature, score, threshold, count, kmax, H, N,
-                               done_ctr, host_slot, seq);
-        }
-    } else if (tick && part && !kmax && B <= SPLIT_MAX_B && B <= 64 && K % 4 == 0 && ldt % 4 == 0 && ldb % 4 == 0 &&
-               aligned16(token_attn) && split_enabled()) {
+        rc = with_flag(score_fast(), [&](auto fast) -> int {
+            constexpr bool FAST = decltype(fast)::value;
+            MADTP_ENSURE_MAX_LDS((token_score_kernel<true, FAST>), 140 * 1024);
+            one_workgroup(token_score_kernel<true, FAST>, stage_bytes);
+            return 0;
+        });
+    } else if (tick && part && !kmax && B <= SPLIT_MAX_B && B <= 64 && vec4 && split_enabled()) {
         // long sequence, small batch: G workgroups per sample (column split), so that the launch covers the chip (measured: VQA,
         // 32 samples x 901 tokens, +6.5 % on the whole forward; at 128 samples the one-workgroup kernel already fills half the
         // chip and the repeated phase A costs 2 %)
-#define TS_SPLIT_LAUNCH(G_, FAST_)                                                                                                          \
-    do {                                                                                                                                   \
-        MADTP_ENSURE_MAX_LDS((token_score_split_kernel<G_, FAST_>), (size_t)MAXN * (128 / G_) * sizeof(float));                             \
-        hipLaunchKernelGGL((token_score_split_kernel<G_, FAST_>), dim3(8 * ((B + 7) / 8) * G_), dim3(512),                                  \
-                           (size_t)(N - 1) * (128 / G_) * sizeof(float), (hipStream_t)stream, colsum_part, n_row_tiles, p0, onorm,        \
-                           token_attn, ldt, ldb, K, temperature, score, threshold, count, H, N, done_ctr, host_slot, seq, tick, part, B); \
-    } while (0)
-        const bool fast = score_fast();  // (the fast precision modes' score arithmetic, madtp_set_score_fast)
-        if (B <= 32) { if (fast) TS_SPLIT_LAUNCH(8, true); else TS_SPLIT_LAUNCH(8, false); }
-        else { if (fast) TS_SPLIT_LAUNCH(4, true); else TS_SPLIT_LAUNCH(4, false); }
-#undef TS_SPLIT_LAUNCH
+        auto split = [&](auto groups, auto fast) -> int {
+            constexpr int G = decltype(groups)::value;
+            constexpr bool FAST = decltype(fast)::value;
+            MADTP_ENSURE_MAX_LDS((token_score_split_kernel<G, FAST>), (size_t)MAXN * (128 / G) * sizeof(float));
+            hipLaunchKernelGGL((token_score_split_kernel<G, FAST>), dim3(8 * ((B + 7) / 8) * G), dim3(512),
+                               (size_t)(N - 1) * (128 / G) * sizeof(float), (hipStream_t)stream, colsum_part, n_row_tiles, p0, onorm,
+                               token_attn, ldt, ldb, K, temperature, score, threshold, count, H, N, done_ctr, host_slot, seq, tick, part, B);
+            return 0;
+        };
+        rc = with_flag(score_fast(), [&](auto fast) -> int {
+            return B <= 32 ? split(std::integral_constant<int, 8>{}, fast) : split(std::integral_constant<int, 4>{}, fast);
+        });
     } else {
-        hipLaunchKernelGGL(token_score_kernel<false>, dim3(B), dim3(512), 0, (hipStream_t)stream, colsum_part, n_row_tiles, p0,
-                           onorm, token_attn, ldt, ldb, K, temperature, score, threshold, count, kmax, H, N, done_ctr, host_slot,
-                           seq);
+        one_workgroup(token_score_kernel<false>, 0);
     }
+    if (rc) return rc;
     MADTP_LAUNCH_CHECK();
     return 0;
 }
@@ -1695,31 +1625,11 @@ extern "C" int madtp_debug_read_ts(long long* out) {
 int madtp_i_token_score_dev(const float* colsum_part, const float* p0, const float* onorm, const float* logits, int ldt, int K,
                             float temperature, float* score, float* threshold, int32_t* count, int B, int H, int N_max,
                             int32_t* dims_l, int32_t* ticket, void* stream) {
-    if (!colsum_part || !p0 || !onorm || !logits || !score || !threshold || !count || !dims_l || !ticket) return MADTP_E_BADARG;
-    if (B <= 0 || H <= 0 || N_max < 2 || !(temperature > 0.f)) return MADTP_E_BADARG;
-    if (N_max - 1 > MAXN || K > 128 || K <= 0 || ldt < K) return MADTP_E_SHAPE;
-    const size_t stage_bytes = (size_t)(N_max - 1) * K * sizeof(float);
-    const bool staged = K % 4 == 0 && ldt % 4 == 0 && aligned16(logits) && stage_bytes <= 140 * 1024;
-    const float* ta = logits + ldt;  // row 0 of every sample is the CLS token
-    if (staged) {  // (the same kernel variant as the host-side path takes at any n <= N_max - 1: same arithmetic)
-        if (score_fast()) {
-            MADTP_ENSURE_MAX_LDS((token_score_kernel<true, true>), 140 * 1024);
-            hipLaunchKernelGGL((token_score_kernel<true, true>), dim3(B), dim3(512), stage_bytes, (hipStream_t)stream, colsum_part,
-                               (N_max + 15) / 16, p0, onorm, ta, ldt, N_max * ldt, K, temperature, score, threshold, count,
-                               (int32_t*)nullptr, H, N_max, ticket, (int32_t*)nullptr, 0, dims_l);
-        } else {
-            MADTP_ENSURE_MAX_LDS(token_score_kernel<true>, 140 * 1024);
-            hipLaunchKernelGGL(token_score_kernel<true>, dim3(B), dim3(512), stage_bytes, (hipStream_t)stream, colsum_part,
-                               (N_max + 15) / 16, p0, onorm, ta, ldt, N_max * ldt, K, temperature, score, threshold, count,
-                               (int32_t*)nullptr, H, N_max, ticket, (int32_t*)nullptr, 0, dims_l);
-        }
-    } else {
-        hipLaunchKernelGGL(token_score_kernel<false>, dim3(B), dim3(512), 0, (hipStream_t)stream, colsum_part, (N_max + 15) / 16, p0,
-                           onorm, ta, ldt, N_max * ldt, K, temperature, score, threshold, count, (int32_t*)nullptr, H, N_max, ticket,
-                           (int32_t*)nullptr, 0, dims_l);
-    }
-    MADTP_LAUNCH_CHECK();
-    return 0;
+    if (!logits || !dims_l || !ticket) return MADTP_E_BADARG;
+    // token_attn = rows 1.. of each sample (row 0 is the CLS token) of the dense [B * N_max, ldt] logits.  Variant and staging are
+    // chosen for N_max, the same as the host-side path takes at any n <= N_max - 1: same arithmetic.
+    return token_score_launch(colsum_part, (N_max + 15) / 16, p0, onorm, logits + ldt, ldt, N_max * ldt, K, temperature, score, threshold,
+                              count, nullptr, B, H, N_max, ticket, nullptr, 0, stream, nullptr, nullptr, dims_l);
 }
 
 int madtp_i_token_select_dev(const float* score, int64_t* indices, int64_t* indices_sort, int32_t* dst_pos, float* merge_w, int B,
@@ -1829,53 +1739,32 @@ extern "C" int madtp_query_att_ft(const float* token_attn, int ldt, int ldb, int
 }
 
 static int att_ft_multi_impl(const madtp_att_ft_seg* segs, int nseg, int K, float* out, float* stats_ws, float inv_sqrt_sd,
-                             int accumulate, int B, int dim, bool split, void* stream);
-
-extern "C" int madtp_query_att_ft_multi(const madtp_att_ft_seg* segs, int nseg, int K, float* out, float* stats_ws,
-                                        float inv_sqrt_sd, int accumulate, int B, int dim, void* stream) {
-    return att_ft_multi_impl(segs, nseg, K, out, stats_ws, inv_sqrt_sd, accumulate, B, dim, false, stream);
-}
-
-extern "C" int madtp_query_att_ft_multi_split(const madtp_att_ft_seg* segs, int nseg, int K, float* out, float* stats_ws,
-                                              float inv_sqrt_sd, int accumulate, int B, int dim, void* stream) {
-    if (!stats_ws) return MADTP_E_BADARG;
-    return att_ft_multi_impl(segs, nseg, K, out, stats_ws, inv_sqrt_sd, accumulate, B, dim, true, stream);
-}
-
-static int att_ft_multi_impl(const madtp_att_ft_seg* segs, int nseg, int K, float* out, float* stats_ws, float inv_sqrt_sd,
                              int accumulate, int B, int dim, bool split, void* stream) {
     if (!segs || !out || nseg < 1 || B <= 0) return MADTP_E_BADARG;
     if (K <= 0 || K > 112 || dim % AB_COLS) return MADTP_E_SHAPE;
-    if (!stats_ws) {  // parity modes: exact-f32 arithmetic, the per-layer summation order kept (see the kernel)
-        if (dim % 256) return MADTP_E_SHAPE;
-        for (int first = 0; first < nseg; first += AB_MAXSEG) {
-            AttFtSegs a;
-            a.nseg = nseg - first < AB_MAXSEG ? nseg - first : AB_MAXSEG;
-            for (int i = 0; i < a.nseg; ++i) {
-                const madtp_att_ft_seg& g = segs[first + i];
-                if (!g.token_attn || !g.ft || g.n < 1) return MADTP_E_BADARG;
-                if (g.ldt_row < K) return MADTP_E_SHAPE;
-                a.s[i] = AttFtSeg{g.token_attn, g.ft, g.n, g.ldt_row, g.ldt_batch, g.ldf_row, g.ldf_batch};
-            }
-            hipLaunchKernelGGL(query_att_ft_exact_multi_kernel, dim3(dim / 256, B), dim3(256), 0, (hipStream_t)stream, a, K, out,
-                               inv_sqrt_sd, (accumulate || first > 0) ? 1 : 0, dim);
-            MADTP_LAUNCH_CHECK();
-        }
-        return 0;
-    }
+    // no statistics workspace: the parity modes' exact-f32 kernel (the per-layer summation order kept, see the kernel); otherwise
+    // the MFMA kernels, which read logits and token rows as float4s
+    const bool mma = stats_ws != nullptr;
+    if (!mma && dim % 256) return MADTP_E_SHAPE;
     for (int first = 0; first < nseg; first += AB_MAXSEG) {
         AttFtSegs a;
         a.nseg = nseg - first < AB_MAXSEG ? nseg - first : AB_MAXSEG;
         for (int i = 0; i < a.nseg; ++i) {
             const madtp_att_ft_seg& g = segs[first + i];
             if (!g.token_attn || !g.ft || g.n < 1) return MADTP_E_BADARG;
-            if (g.ldt_row < ((K + 3) & ~3)) return MADTP_E_SHAPE;
-            if (g.ldf_row % 4 || g.ldf_batch % 4 || !aligned16(g.ft)) return MADTP_E_ALIGN;
-            if (g.ldt_row % 4 || g.ldt_batch % 4 || !aligned16(g.token_attn)) return MADTP_E_ALIGN;
+            if (g.ldt_row < (mma ? (K + 3) & ~3 : K)) return MADTP_E_SHAPE;
+            if (mma && (g.ldf_row % 4 || g.ldf_batch % 4 || !aligned16(g.ft))) return MADTP_E_ALIGN;
+            if (mma && (g.ldt_row % 4 || g.ldt_batch % 4 || !aligned16(g.token_attn))) return MADTP_E_ALIGN;
             a.s[i] = AttFtSeg{g.token_attn, g.ft, g.n, g.ldt_row, g.ldt_batch, g.ldf_row, g.ldf_batch};
         }
-        float* stats = stats_ws + (size_t)first * B * 256;
         const int acc_flag = (accumulate || first > 0) ? 1 : 0;
+        if (!mma) {
+            hipLaunchKernelGGL(query_att_ft_exact_multi_kernel, dim3(dim / 256, B), dim3(256), 0, (hipStream_t)stream, a, K, out,
+                               inv_sqrt_sd, acc_flag, dim);
+            MADTP_LAUNCH_CHECK();
+            continue;
+        }
+        float* stats = stats_ws + (size_t)first * B * 256;
         if (split) {
             MADTP_ENSURE_MAX_LDS(query_att_ft_mma_kernel<true>, att_ft_mma_lds(true));
             hipLaunchKernelGGL(att_ft_stats_kernel<true>, dim3(a.nseg, B), dim3(256), 0, (hipStream_t)stream, a, K, inv_sqrt_sd, stats);
@@ -1890,6 +1779,17 @@ static int att_ft_multi_impl(const madtp_att_ft_seg* segs, int nseg, int K, floa
         MADTP_LAUNCH_CHECK();
     }
     return 0;
+}
+
+extern "C" int madtp_query_att_ft_multi(const madtp_att_ft_seg* segs, int nseg, int K, float* out, float* stats_ws,
+                                        float inv_sqrt_sd, int accumulate, int B, int dim, void* stream) {
+    return att_ft_multi_impl(segs, nseg, K, out, stats_ws, inv_sqrt_sd, accumulate, B, dim, false, stream);
+}
+
+extern "C" int madtp_query_att_ft_multi_split(const madtp_att_ft_seg* segs, int nseg, int K, float* out, float* stats_ws,
+                                              float inv_sqrt_sd, int accumulate, int B, int dim, void* stream) {
+    if (!stats_ws) return MADTP_E_BADARG;
+    return att_ft_multi_impl(segs, nseg, K, out, stats_ws, inv_sqrt_sd, accumulate, B, dim, true, stream);
 }
 
 extern "C" int madtp_vector_gather(const float* vectors, const int64_t* indices, float* out, int B, int L, int K, int D,
