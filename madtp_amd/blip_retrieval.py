@@ -412,13 +412,20 @@ def all_gather_scores(score_i2t, score_t2i):
 
 
 @torch.no_grad()
-def evaluate(model, data_loader, device, config, temperature=0, rank=0, world_size=1, text_bs=256, kv_cache=True):
+def evaluate(model, data_loader, device, config, temperature=0, rank=0, world_size=1, text_bs=256, kv_cache=True,
+             candidates="dense"):
     """compress_retrieval_dtp.py evaluate() :84-207 -> (score_matrix_i2t, score_matrix_t2i) as numpy arrays and the GFLOPs
     placeholder (0.0: the reference's fvcore count of the TRAINING forward is out of scope, harness.nlvr_forward_flops is
     the analytic counter of this repo).  rank / world_size select this process's row slices exactly as :158-162 / :181-183
     do; the caller all-reduces the two matrices (SUM) when world_size > 1, as :200-203.
     kv_cache: project the image tokens to every layer's cross-attention [k|v] ONCE (EncoderKVCache) and let the re-ranking
-    batches index that cache; False reproduces the reference's data flow (each pair re-projects its image)."""
+    batches index that cache; False reproduces the reference's data flow (each pair re-projects its image).
+    candidates: "dense" (the default, the reference's data flow) forms sims_matrix and takes topk(k_test) of one row per loop
+    iteration; "device" takes the k_test candidates of all rows, in both directions, from two search.topk_embeds calls before the
+    loops and never forms sims_matrix (its ITC term is the exact-f32 score of that kernel, its order among equal scores the one
+    of madtp_search.h)."""
+    if candidates not in ("dense", "device"):
+        raise ValueError(f"candidates = {candidates!r}: expected 'dense' or 'device'")
     k_test = config['k_test']
     sd = model.space_dict
     texts = data_loader.dataset.text
@@ -458,19 +465,28 @@ def evaluate(model, data_loader, device, config, temperature=0, rank=0, world_si
                                      return_dict=True, space_dict=sd, temperature=temperature)[0]
         return model.itm_score(out.last_hidden_state[:, 0, :])
 
-    sims_matrix = image_embeds @ text_embeds.t()  # :155
-    n_img = sims_matrix.shape[0]
+    n_img = image_embeds.shape[0]
+    if candidates == "device":
+        from . import search
+        if k_test > min(n_img, num_text):  # (what topk() of the dense path refuses)
+            raise RuntimeError(f"k_test = {k_test} exceeds the {n_img} images or the {num_text} texts")
+        i2t_sim, i2t_idx = search.topk_embeds(image_embeds.float(), text_embeds.float(), k_test)
+        t2i_sim, t2i_idx = search.topk_embeds(text_embeds.float(), image_embeds.float(), k_test)
+        top_i2t, top_t2i = (lambda i: (i2t_sim[i], i2t_idx[i])), (lambda i: (t2i_sim[i], t2i_idx[i]))
+    else:
+        sims_matrix = image_embeds @ text_embeds.t()  # :155
+        sims_t = sims_matrix.t()
+        top_i2t, top_t2i = (lambda i: sims_matrix[i].topk(k=k_test, dim=0)), (lambda i: sims_t[i].topk(k=k_test, dim=0))
     score_i2t = torch.full((n_img, num_text), -100.0, device=device)
     start, end = rank_rows(n_img, rank, world_size)
     for i in range(start, end):  # :164-174
-        topk_sim, topk_idx = sims_matrix[i].topk(k=k_test, dim=0)
+        topk_sim, topk_idx = top_i2t(i)
         score_i2t[i, topk_idx] = rerank(text_ids[topk_idx], text_atts[topk_idx],
                                         torch.full((k_test,), i, dtype=torch.long, device=device)) + topk_sim
 
-    sims_t = sims_matrix.t()
     score_t2i = torch.full((num_text, n_img), -100.0, device=device)
     start, end = rank_rows(num_text, rank, world_size)
     for i in range(start, end):  # :186-198
-        topk_sim, topk_idx = sims_t[i].topk(k=k_test, dim=0)
+        topk_sim, topk_idx = top_t2i(i)
         score_t2i[i, topk_idx] = rerank(text_ids[i].repeat(k_test, 1), text_atts[i].repeat(k_test, 1), topk_idx) + topk_sim
     return score_i2t.cpu().numpy(), score_t2i.cpu().numpy(), 0.0

@@ -6,28 +6,9 @@
 #include <algorithm>
 #include <limits.h>
 
-#include "common.h"
+#include "eval_device.h"  // the constants, RankArgs and rank_tile_products, the one product routine (shared with search.hip)
 
 namespace {
-
-constexpr int RK_RT = 32;        // query rows per workgroup: two 16-row MFMA blocks that share every key fragment
-constexpr int RK_CT = 64;        // key columns per tile, 16 per wave
-constexpr int RK_DC = 64;        // features per staged chunk
-constexpr int RK_LD = 68;        // floats per LDS row: 16-byte aligned rows, 68 r mod 64 = 4 r
-constexpr int RK_THREADS = 256;
-constexpr int RK_MAXT = 16;      // targets per row
-constexpr int RK_MAX_SPLITS = 1024;
-
-struct RankArgs {
-    const float *q, *keys;
-    int ldq, ldk, nq, nk, D;
-    int cap;  // targets the workspace holds per split = the stride of part
-    const int32_t *tgt_ptr, *tgt_idx;
-    int32_t *rank_row, *rank_tgt;
-    float* score_tgt;
-    int32_t* part;  // [splits, cap] counts
-    int splits, tiles_per_split;
-};
 
 // targets of row r: first CSR position and count.  Pointers that leave [0, min(tgt_ptr[nq], cap)] or run backwards give an
 // empty row; targets past the 16th are ignored.
@@ -35,52 +16,6 @@ __device__ __forceinline__ void rank_row_span(const RankArgs& a, int r, int& lo,
     lo = a.tgt_ptr[r];
     const int hi = a.tgt_ptr[r + 1];
     n = (lo < 0 || hi > min(a.tgt_ptr[a.nq], a.cap) || hi < lo) ? 0 : min(hi - lo, RK_MAXT);
-}
-
-// The one product routine of this file: acc0 / acc1 = rows [r0, r0 + 16) / [r0 + 16, r0 + 32) of q against the 64 key rows
-// krow[] that the caller names (thread t stages feature quad 4 (t % 16) of the tile's columns t / 16 + 16 i; -1 = a column of
-// zeros).  Lane (c, g) = (l & 15, l >> 4) of wave w holds [row 4 g + i][column 16 w + c] in register i.  Every element is the
-// fmaf chain over the features in the order chunk, j, e, g of feature 64 chunk + 16 j + 4 g + e - a function of the two rows
-// alone, not of the column's place in a tile - so a score computed for a gathered target column and the score the counting
-// pass forms for the same key row (or a byte copy of it) are the same bits.
-// The next chunk's global loads are issued before the products of the current one.
-__device__ __forceinline__ void rank_tile_products(const RankArgs& a, int r0, const int (&krow)[4], float (*Qs)[RK_LD],
-                                                   float (*Ks)[RK_LD], f32x4& acc0, f32x4& acc1) {
-    const int t = threadIdx.x, w = t >> 6, c = t & 15, g = (t >> 4) & 3;
-    const int sr = t >> 4, d4 = (t & 15) * 4;
-    const int ndc = a.D / RK_DC;
-    f32x4 qreg[2], kreg[4];
-    auto fetch = [&](int dc) {
-        for (int i = 0; i < 2; ++i) {
-            const int row = r0 + sr + 16 * i;
-            qreg[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (row < a.nq) qreg[i] = *(const f32x4*)(a.q + (size_t)row * a.ldq + dc * RK_DC + d4);
-        }
-        for (int i = 0; i < 4; ++i) {
-            kreg[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (krow[i] >= 0) kreg[i] = *(const f32x4*)(a.keys + (size_t)krow[i] * a.ldk + dc * RK_DC + d4);
-        }
-    };
-    acc0 = f32x4{0.f, 0.f, 0.f, 0.f};
-    acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
-    fetch(0);
-    for (int dc = 0; dc < ndc; ++dc) {
-        for (int i = 0; i < 2; ++i) *(f32x4*)&Qs[sr + 16 * i][d4] = qreg[i];
-        for (int i = 0; i < 4; ++i) *(f32x4*)&Ks[sr + 16 * i][d4] = kreg[i];
-        __syncthreads();
-        if (dc + 1 < ndc) fetch(dc + 1);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const f32x4 qa0 = *(const f32x4*)&Qs[c][16 * j + 4 * g], qa1 = *(const f32x4*)&Qs[16 + c][16 * j + 4 * g];
-            const f32x4 kb = *(const f32x4*)&Ks[16 * w + c][16 * j + 4 * g];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(qa0[e], kb[e], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(qa1[e], kb[e], acc1, 0, 0, 0);
-            }
-        }
-        lds_barrier();  // the tiles are free again; the loads in flight stay in flight
-    }
 }
 
 // ---- pass 1: the target scores.  One workgroup per row tile; its rows' targets are gathered as key columns, slot
