@@ -27,8 +27,8 @@ from . import abi, hip, preprocess
 from .preprocess import MEAN, STD
 
 HEADER = os.path.join(os.path.dirname(abi.HEADER), "madtp_augment.h")
-with open(HEADER) as _f:
-    SIGNATURES, _, DEFINES = abi.parse(_f.read())  # the one declaration of the madtp_augment_* entry points
+# the one declaration of the madtp_augment_* entry points; lib() sets them on preprocess.lib()'s handle (the resize is the image stage's)
+SIGNATURES, DEFINES, lib = abi.bind("madtp_augment.h", "madtp_augment_abi_version", needs=preprocess.lib)
 ABI_VERSION = DEFINES["MADTP_AUGMENT_ABI_VERSION"]
 FIELDS, MAX_PIXELS, FILL = DEFINES["MADTP_AUGMENT_FIELDS"], DEFINES["MADTP_AUGMENT_MAX_PIXELS"], DEFINES["MADTP_AUGMENT_FILL"]
 _F_OP, _F_TABLE, _F_A0 = DEFINES["MADTP_AUGMENT_F_OP"], DEFINES["MADTP_AUGMENT_F_TABLE"], DEFINES["MADTP_AUGMENT_F_A0"]
@@ -39,24 +39,6 @@ OP_COPY, OP_TABLE, OP_EQUALIZE, OP_AUTOCONTRAST, OP_WARP = (DEFINES["MADTP_AUGME
 REFERENCE_AUGS = ("Identity", "AutoContrast", "Brightness", "Sharpness", "Equalize", "ShearX", "ShearY", "TranslateX", "TranslateY",
                   "Rotate")
 MAX_LEVEL, TRANSLATE_CONST, REPLACE = 10, 10, (FILL, FILL, FILL)  # transform/randaugment.py's constants
-
-_bound = False
-
-
-def lib():
-    """hip.load()'s handle with the madtp_augment_* signatures set on it (no GPU needed)"""
-    global _bound
-    h = preprocess.lib()
-    if not _bound:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(h, name)  # AttributeError => header/library mismatch
-            fn.restype = res
-            fn.argtypes = args
-        if h.madtp_augment_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"libmadtp_hip augment ABI {h.madtp_augment_abi_version()} != binding {ABI_VERSION}; rebuild")
-        _bound = True
-    return h
-
 
 # ---- the draws ---------------------------------------------------------------------------------------------------------------------
 def level_to_args(name, level, rng):
@@ -377,11 +359,4 @@ class RawTrainBatch:
 
 def collate(samples, size, scale=(0.5, 1.0), N=2, M=5, augs=REFERENCE_AUGS, mean=MEAN, std=STD):
     """collate_fn of a training loader (bind `size` with functools.partial): preprocess.collate with RawTrainBatch for the images"""
-    from torch.utils.data import default_collate
-    make = lambda col: RawTrainBatch(col, size, scale, N, M, augs, mean, std)
-    first = samples[0]
-    if preprocess._is_raw(first):
-        return make(samples)
-    if isinstance(first, (tuple, list)):
-        return [make(col) if preprocess._is_raw(col[0]) else default_collate(list(col)) for col in zip(*samples)]
-    return default_collate(samples)
+    return preprocess.collate_with(samples, preprocess._is_raw, lambda col: RawTrainBatch(col, size, scale, N, M, augs, mean, std))

@@ -13,10 +13,10 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmadtp_hip.so")
 SOURCES = ["gemm.hip", "gemm_pp.hip", "attention.hip", "norm.hip", "prune.hip", "layers.hip", "lmhead.hip", "backward.hip", "retrieval.hip", "clip.hip", "eval.hip", "optim.hip", "image.hip", "augment.hip", "jpeg.hip", "search.hip", "jpeg_huff.hip"]
-HEADERS = ["common.h", "internal.h", "gemm_device.h", "gemm_plan.h", "gemm_table.h", "attn_plan.h", "image_device.h", "jpeg_entropy.h", "jpeg_huff_device.h", "eval_device.h",
-           os.path.join("..", "..", "include", "madtp_hip.h"), os.path.join("..", "..", "include", "madtp_image.h"),
-           os.path.join("..", "..", "include", "madtp_augment.h"), os.path.join("..", "..", "include", "madtp_jpeg.h"),
-           os.path.join("..", "..", "include", "madtp_search.h"), os.path.join("..", "..", "include", "madtp_jhuff.h")]
+INCLUDE = os.path.join("..", "..", "include")
+# what is on disk, as paths from csrc/: a header nobody listed cannot leave a stale library
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + \
+    sorted(os.path.join(INCLUDE, f) for f in os.listdir(os.path.join(CSRC, INCLUDE)) if f.endswith(".h"))
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 
 

@@ -14,7 +14,6 @@ Accepted: SOF0 / SOF1 8-bit Huffman files of one interleaved scan, grayscale or 
 Everything else is UnsupportedJpeg naming the reason (read(..., other="pil") hands such a file to Pillow instead); a malformed
 stream is CorruptJpeg, never a partial image.  There is no fallback: without a GPU the decoder raises."""
 import collections
-import concurrent.futures
 import functools
 import os
 import threading
@@ -22,18 +21,16 @@ import threading
 import numpy as np
 import torch
 
-from . import abi, hip, preprocess
+from . import abi, hip, preprocess, staging
+from .staging import MAX_WORKERS, align as _align
 
 HEADER = os.path.join(os.path.dirname(abi.HEADER), "madtp_jpeg.h")
-with open(HEADER) as _f:
-    SIGNATURES, _, DEFINES = abi.parse(_f.read())  # the one declaration of the madtp_jpeg_* entry points
+# the one declaration of the madtp_jpeg_* entry points; lib() is hip.load()'s handle with them set on it (no GPU needed)
+SIGNATURES, DEFINES, lib = abi.bind("madtp_jpeg.h", "madtp_jpeg_abi_version")
 ABI_VERSION = DEFINES["MADTP_JPEG_ABI_VERSION"]
 FIELDS, INFO_FIELDS = DEFINES["MADTP_JPEG_FIELDS"], DEFINES["MADTP_JPEG_INFO_FIELDS"]
 _F = {k[len("MADTP_JPEG_F_"):]: v for k, v in DEFINES.items() if k.startswith("MADTP_JPEG_F_")}
 _I = {k[len("MADTP_JPEG_I_"):]: v for k, v in DEFINES.items() if k.startswith("MADTP_JPEG_I_")}
-MAX_WORKERS = 16
-
-_bound = False
 
 
 class UnsupportedJpeg(ValueError):
@@ -42,21 +39,6 @@ class UnsupportedJpeg(ValueError):
 
 class CorruptJpeg(ValueError):
     """a malformed JPEG stream"""
-
-
-def lib():
-    """hip.load()'s handle with the madtp_jpeg_* signatures set on it (no GPU needed)"""
-    global _bound
-    h = hip.load()
-    if not _bound:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(h, name)  # AttributeError => header/library mismatch
-            fn.restype = res
-            fn.argtypes = args
-        if h.madtp_jpeg_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"libmadtp_hip jpeg ABI {h.madtp_jpeg_abi_version()} != binding {ABI_VERSION}; rebuild")
-        _bound = True
-    return h
 
 
 def _raise(code, what):
@@ -84,6 +66,13 @@ def _byte_array(data, what="data"):
     raise ValueError(f"{what}: {type(data).__name__} is not bytes, a 1-D uint8 array or a path")
 
 
+def _set_header(image, info):
+    """the header fields an EntropyImage and a jpeg_device.ScanImage share, from the int32 [INFO_FIELDS] of madtp_jpeg_inspect"""
+    image.width, image.height, image.components = int(info[_I["WIDTH"]]), int(info[_I["HEIGHT"]]), int(info[_I["COMPONENTS"]])
+    image.hs, image.vs = int(info[_I["HS"]]), int(info[_I["VS"]])
+    image.blocks_x, image.blocks_y, image.restart_interval = int(info[_I["BLOCKS_X"]]), int(info[_I["BLOCKS_Y"]]), int(info[_I["RESTART"]])
+
+
 class EntropyImage:
     """What the host stage makes of one file: the header fields, `qtables` (uint16 [3, 64], natural order, rows of absent components
     0) and `coef` (int16 [blocks, 64]: component after component, each [blocks_y, blocks_x] blocks, column-major within a block).
@@ -91,9 +80,7 @@ class EntropyImage:
     __slots__ = ("width", "height", "components", "hs", "vs", "blocks_x", "blocks_y", "restart_interval", "qtables", "coef")
 
     def __init__(self, info, qtables, coef):
-        self.width, self.height, self.components = int(info[_I["WIDTH"]]), int(info[_I["HEIGHT"]]), int(info[_I["COMPONENTS"]])
-        self.hs, self.vs = int(info[_I["HS"]]), int(info[_I["VS"]])
-        self.blocks_x, self.blocks_y, self.restart_interval = int(info[_I["BLOCKS_X"]]), int(info[_I["BLOCKS_Y"]]), int(info[_I["RESTART"]])
+        _set_header(self, info)
         self.qtables, self.coef = qtables, coef
 
     def __getstate__(self):  # (torch's pickling has no uint16 storage: the small table travels as a numpy array)
@@ -136,15 +123,13 @@ def entropy_decode(data, what="entropy_decode"):
     return EntropyImage(info, torch.from_numpy(q), coef)
 
 
-def read(source, other="raise"):
-    """a path or bytes -> EntropyImage: the dataset's replacement for Image.open(path).convert('RGB').  other="pil": a file this
-    decoder REFUSES (UnsupportedJpeg: progressive, CMYK, ...) is decoded by Pillow to preprocess.raw_image()'s uint8 [h,w,3] tensor,
-    which the decoder passes through; a corrupt file raises either way."""
+def _read_with(stage, source, other):
+    """read() of this module and of jpeg_device: `stage` is the host stage, entropy_decode or jpeg_device.prepare_scan"""
     if other not in ("raise", "pil"):
         raise ValueError(f"read: other={other!r} is not 'raise' or 'pil'")
     buf = _byte_array(source, "read")
     try:
-        return entropy_decode(buf, str(source) if isinstance(source, (str, os.PathLike)) else "read")
+        return stage(buf, str(source) if isinstance(source, (str, os.PathLike)) else "read")
     except UnsupportedJpeg:
         if other != "pil":
             raise
@@ -153,11 +138,176 @@ def read(source, other="raise"):
     return preprocess.raw_image(Image.open(io.BytesIO(buf.tobytes())))
 
 
-def _align(n, a):
-    return (n + a - 1) // a * a
+def read(source, other="raise"):
+    """a path or bytes -> EntropyImage: the dataset's replacement for Image.open(path).convert('RGB').  other="pil": a file this
+    decoder REFUSES (UnsupportedJpeg: progressive, CMYK, ...) is decoded by Pillow to preprocess.raw_image()'s uint8 [h,w,3] tensor,
+    which the decoder passes through; a corrupt file raises either way."""
+    return _read_with(entropy_decode, source, other)
 
 
-class JpegDecoder:
+# ---- the layout of a batch ---------------------------------------------------------------------------------------------------------
+# what plan_batch needs of madtp_jhuff.h (jpeg_device hands it over: this module does not read that header)
+ScanFormat = collections.namedtuple("ScanFormat", "F FIELDS RECORD_BYTES MAX_BYTES")
+
+# One device buffer per batch, for both decoders:
+#   [ table | quantisation tables | decode-kernel table || coefficients (host route) or Huffman records and files (device route) |
+#     decoded pass-through images ]    <- staged and copied, copy_bytes in all; everything before || is `head`
+#   [ coefficients the decode kernel writes (device route) ]    at coef_at
+#   [ decoded images ]                                          at out_at .. total
+# Records and coefficients lie at multiples of 4 bytes (they do of 16), files and images of 16, planes and the two device-made
+# regions of 256.  shapes: per image ((h, w), offset of its pixels in the buffer); blocks: of every coded image, in `coded`'s order.
+JpegPlan = collections.namedtuple("JpegPlan", "B head table htable table_bytes qtable_at htable_at coded blocks copy_bytes coef_at out_at "
+                                              "total plane_bytes workspace n_idct n_rgb shapes")
+
+
+_ROW = [_F[k] for k in "COEF QTABLE PLANES OUT W H COMPONENTS HS VS BLOCKS_X BLOCKS_Y".split()]
+_HROW = "FILE SIZE SCAN RECORD COEF COMPONENTS HS VS BLOCKS_X BLOCKS_Y RESTART".split()
+
+
+def plan_batch(items, scans=None):
+    """The one place that lays a batch out and fills the MADTP_JPEG_F_* rows (and, with `scans`, a ScanFormat, the MADTP_JHUFF_F_*
+    rows of the device route).  Host arithmetic only, with the library's own size queries.  items: per image ("raw", shape) or
+    ("coded", header, blocks it claims to have or None, None or (file bytes, scan_begin, Huffman record bytes)), where header has the
+    fields of an EntropyImage.  ValueError naming the image whose fields contradict each other."""
+    h = lib()
+    B = len(items)
+    table = np.zeros((B, FIELDS), dtype=np.int64)
+    qtables = np.zeros((B, 3, 8, 8), dtype=np.uint16)
+    qtable_at, htable_at = table.nbytes, table.nbytes + qtables.nbytes
+    coded, rows, hrows, qs, blocks, firsts, places = [], [], [], [], [], [], []
+    coef_bytes = plane_at = plane_sum = raw_bytes = out_bytes = n_idct = n_rgb = 0
+    at = htable_at + (8 * scans.FIELDS * sum(it[0] == "coded" for it in items) if scans else 0)  # the end of `head`
+    for i, it in enumerate(items):
+        # every row has a place in both grids (the search wants non-decreasing prefixes); a decoded image has no workgroup, and the
+        # rest of its row is never read
+        firsts.append((n_idct, n_rgb))
+        if it[0] == "raw":
+            hh, ww = int(it[1][0]), int(it[1][1])
+            raw_bytes = _align(raw_bytes, 16)
+            places.append((hh, ww, raw_bytes))
+            raw_bytes += 3 * hh * ww
+            continue
+        _, im, claimed, scan = it
+        geometry = (im.components, im.hs, im.vs, im.blocks_x, im.blocks_y)
+        nb = int(h.madtp_jpeg_blocks(*geometry))
+        ok = nb >= 1 and claimed in (None, nb) and 1 <= im.width <= 8 * im.blocks_x and 1 <= im.height <= 8 * im.blocks_y
+        if scans is not None:
+            file_bytes, scan_begin, record_bytes = scan
+            ok = ok and 0 <= scan_begin <= file_bytes <= scans.MAX_BYTES and record_bytes == scans.RECORD_BYTES
+        if not ok:
+            raise ValueError(f"image {i}: {'an EntropyImage' if scans is None else 'a ScanImage'} whose fields contradict each other")
+        planes, plane_bytes = _align(plane_at, 256), int(h.madtp_jpeg_plane_bytes(*geometry))
+        coded.append(i)
+        rows.append((coef_bytes, 384 * i, planes, out_bytes, im.width, im.height) + geometry)
+        qs.append(im.qtables.numpy() if torch.is_tensor(im.qtables) else im.qtables)
+        if scans is not None:
+            record = _align(at, 16)
+            at = record + record_bytes + file_bytes  # (a record is a multiple of 16 bytes: the file behind it is aligned as it is)
+            hrows.append((record + record_bytes, file_bytes, scan_begin, record, coef_bytes) + geometry + (im.restart_interval,))
+        places.append((im.height, im.width, out_bytes))
+        blocks.append(nb)
+        coef_bytes += 128 * nb
+        plane_at, plane_sum = planes + plane_bytes, plane_sum + plane_bytes
+        out_bytes += _align(int(h.madtp_jpeg_out_bytes(im.width, im.height)), 16)
+        n_idct += h.madtp_jpeg_idct_groups(nb)
+        n_rgb += h.madtp_jpeg_rgb_groups(im.width, im.height)
+    if scans is None:  # the host route stages the coefficients themselves
+        coef_at, at = at, at + coef_bytes
+    raw_at = _align(at, 16)
+    copy_bytes = at = raw_at + raw_bytes if len(coded) < B else at  # (without a decoded image nothing a launch does not read is copied)
+    if scans is not None:
+        coef_at = _align(at, 256)
+        at = coef_at + coef_bytes
+    out_at = _align(at, 256)
+    htable = np.zeros((len(coded), scans.FIELDS) if scans else (0, 1), dtype=np.int64)
+    table[:, [_F["FIRST_IDCT"], _F["FIRST_RGB"]]] = firsts
+    if coded:
+        table[np.ix_(coded, _ROW)] = rows
+        qtables[coded] = np.asarray(qs, dtype=np.uint16).reshape(-1, 3, 8, 8).transpose(0, 1, 3, 2)  # column-major, as the coefficients
+        if scans is not None:
+            htable[:, [scans.F[k] for k in _HROW]] = hrows
+    head = np.concatenate([a.reshape(-1).view(np.uint8) for a in (table, qtables, htable)])
+    shapes = [((hh, ww), (out_at if it[0] == "coded" else raw_at) + o) for it, (hh, ww, o) in zip(items, places)]
+    return JpegPlan(B, head, table, htable, table.nbytes, qtable_at, htable_at, coded, blocks, copy_bytes, coef_at, out_at, out_at + out_bytes,
+                    plane_sum, int(h.madtp_jpeg_workspace(B, plane_sum)), n_idct, n_rgb, shapes)
+
+
+class _Prepared:
+    """a prepared batch reads its plan's fields as its own: batch.B, batch.shapes, batch.table_bytes, batch.out_at, batch.copy_bytes"""
+    __slots__ = ()
+
+    def __getattr__(self, name):
+        return getattr(self.plan, name)
+
+
+class PreparedJpegBatch(_Prepared, collections.namedtuple("PreparedJpegBatch", "packed planes plan")):
+    """what prepare() leaves on the device: the packed buffer of the plan, the plane scratch, and the plan with the launches' arguments"""
+    __slots__ = ()
+
+
+class _BatchDecoder:
+    """What JpegDecoder and jpeg_device.DeviceJpegDecoder share: the pool, the staging ring (two pinned buffers guarded by events, as
+    ImagePipeline's), the one copy of a planned batch, and the IDCT and colour launches."""
+
+    def __init__(self, device, workers, thread_name):
+        self.device = torch.device(device)
+        self._pool = staging.Pool(workers, thread_name)
+        self.workers = self._pool.workers
+        self._ring = staging.StagingRing()
+        self._lock = threading.Lock()
+
+    def __call__(self, items):
+        return self.run(self.prepare(items))
+
+    @staticmethod
+    def _decoded(it, i):
+        """an already decoded uint8 [h,w,3] item -> its host array, None for an item of another kind"""
+        if not ((torch.is_tensor(it) or isinstance(it, np.ndarray)) and it.ndim == 3):
+            return None
+        host, _ = preprocess._as_uint8_hw3(it, i)
+        if host is None:
+            raise ValueError(f"image {i}: a decoded image must be a host array (device images need no decoder)")
+        return host
+
+    def _need_gpu(self, for_cpu_checking):
+        if self.device.type != "cuda" or not torch.cuda.is_available():
+            raise RuntimeError(f"{type(self).__name__} on {self.device}: madtp_amd runs only on an MI355X through the HIP kernels (no CPU / "
+                               f"eager fallback).  {for_cpu_checking}")
+
+    def _send(self, plan, decoded, fill):
+        """the plan's head, the decoded images {index: host array} and what fill(view, stage) writes go into the next staging buffer
+        and, in one asynchronous copy on the current stream, to the device -> (packed buffer, plane scratch)"""
+        with self._lock, torch.cuda.device(self.device if self.device.index is not None else torch.cuda.current_device()):
+            device = torch.device("cuda", torch.cuda.current_device())
+            turn, stage = self._ring.acquire(plan.copy_bytes)
+            view = stage.numpy()
+            view[:plan.head.size] = plan.head
+            for i, host in decoded.items():
+                o = plan.shapes[i][1]
+                np.copyto(view[o:o + host.size].reshape(host.shape), host)
+            fill(view, stage)  # (an exception of any item surfaces here, before the copy and the launches)
+            packed = torch.empty(max(plan.total, 1), dtype=torch.uint8, device=device)
+            packed[:plan.copy_bytes].copy_(stage[:plan.copy_bytes], non_blocking=True)
+            self._ring.sent(turn)
+            planes = torch.empty(max(plan.workspace, 1), dtype=torch.uint8, device=device)
+        return packed, planes
+
+    def _pixel_launches(self, batch):
+        h = lib()
+        p, plan = batch.packed.data_ptr(), batch.plan
+        if not plan.n_idct:
+            return []
+        return [("madtp_jpeg_idct_batch", lambda stream: h.madtp_jpeg_idct_batch(
+                    p + plan.coef_at, p + plan.qtable_at, p, batch.planes.data_ptr(), plan.B, plan.n_idct, stream)),
+                ("madtp_jpeg_rgb_batch", lambda stream: h.madtp_jpeg_rgb_batch(
+                    batch.planes.data_ptr(), p, p + plan.out_at, plan.B, plan.n_rgb, stream))]
+
+    @staticmethod
+    def _images(batch):
+        return [batch.packed[o:o + 3 * hh * ww].view(hh, ww, 3) for (hh, ww), o in batch.plan.shapes]
+
+
+class JpegDecoder(_BatchDecoder):
     """JPEG files -> uint8 [h,w,3] tensors on `device`, views of one packed buffer: one copy and two launches per batch.
 
     An item is an EntropyImage, the bytes of a file (entropy-decoded here by `workers` threads - ctypes releases the GIL; at most
@@ -166,154 +316,53 @@ class JpegDecoder:
     asynchronous copy on the current stream, which the two launches follow.  Every item is checked before anything is launched."""
 
     def __init__(self, device="cuda", workers=8):
-        self.device = torch.device(device)
-        self.workers = max(1, min(int(workers), MAX_WORKERS))
-        self._pool = None
-        self._stage = [None, None]
-        self._events = [None, None]
-        self._turn = 0
-        self._lock = threading.Lock()
-
-    def _staging(self, nbytes):
-        i = self._turn
-        self._turn ^= 1
-        if self._events[i] is not None:
-            self._events[i].synchronize()
-        if self._stage[i] is None or self._stage[i].numel() < nbytes:
-            self._stage[i] = torch.empty(max(nbytes, 1 << 20) * 5 // 4, dtype=torch.uint8, pin_memory=True)
-        return i, self._stage[i]
-
-    def _map(self, fn, jobs):
-        if self.workers == 1 or len(jobs) < 2:
-            return [fn(j) for j in jobs]
-        if self._pool is None:
-            self._pool = concurrent.futures.ThreadPoolExecutor(self.workers, thread_name_prefix="madtp-jpeg")
-        futures = [self._pool.submit(fn, j) for j in jobs]
-        concurrent.futures.wait(futures)  # all of them: a failed batch leaves no thread writing into the staging buffer
-        return [f.result() for f in futures]
-
-    def __call__(self, items):
-        return self.run(self.prepare(items))
+        super().__init__(device, workers, "madtp-jpeg")
 
     def prepare(self, items):
         """the checks, the entropy decode of byte items, the packing and the copy -> PreparedJpegBatch for run()"""
         items = list(items)
-        B = len(items)
-        if B < 1:
+        if len(items) < 1:
             raise ValueError("JpegDecoder: an empty batch")
         h = lib()
-        kinds = []  # per item ("coef", EntropyImage, the file's bytes or None) / ("raw", numpy [h,w,3], None)
+        facts, files, decoded = [], {}, {}  # plan_batch's items; the bytes of the items that are files; the decoded images
         for i, it in enumerate(items):
-            if isinstance(it, EntropyImage):
-                kinds.append(("coef", it, None))
-            elif (torch.is_tensor(it) or isinstance(it, np.ndarray)) and it.ndim == 3:
-                host, dev = preprocess._as_uint8_hw3(it, i)
-                if host is None:
-                    raise ValueError(f"image {i}: a decoded image must be a host array (device images need no decoder)")
-                kinds.append(("raw", host, None))
-            else:
-                buf = _byte_array(it, f"image {i}")
-                info, q = _inspect(buf, f"image {i}")
-                kinds.append(("coef", EntropyImage(info, q, None), buf))
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise RuntimeError(f"JpegDecoder on {self.device}: madtp_amd runs only on an MI355X through the HIP kernels (no CPU / "
-                               "eager fallback).  tests/jpeg_ref.py restates the arithmetic for CPU checking.")
-        with self._lock, torch.cuda.device(self.device if self.device.index is not None else torch.cuda.current_device()):
-            device = torch.device("cuda", torch.cuda.current_device())
-            table = np.zeros((B, FIELDS), dtype=np.int64)
-            tb = table.nbytes
-            qb = B * 3 * 64 * 2
-            # the layout: [table | quantisation tables | coefficients | decoded pass-through images] is staged and copied, the
-            # decoded outputs follow in the same device buffer; the planes are scratch of their own
-            blocks = [0] * B
-            coef_at, plane_at, plane_sum, raw_bytes = 0, 0, 0, 0
-            for i, (kind, it, _) in enumerate(kinds):
-                if kind == "raw":
+            if not isinstance(it, EntropyImage):
+                host = self._decoded(it, i)
+                if host is not None:
+                    decoded[i] = host
+                    facts.append(("raw", host.shape))
                     continue
-                row = table[i]
-                blocks[i] = int(h.madtp_jpeg_blocks(it.components, it.hs, it.vs, it.blocks_x, it.blocks_y))
-                if blocks[i] < 1 or not (1 <= it.width <= 8 * it.blocks_x and 1 <= it.height <= 8 * it.blocks_y) or \
-                        (it.coef is not None and tuple(it.coef.shape) != (blocks[i], 64)):
-                    raise ValueError(f"image {i}: an EntropyImage whose fields contradict each other")
-                row[_F["COEF"]], row[_F["QTABLE"]], row[_F["PLANES"]] = coef_at, i * 384, _align(plane_at, 256)
-                row[_F["W"]], row[_F["H"]], row[_F["COMPONENTS"]] = it.width, it.height, it.components
-                row[_F["HS"]], row[_F["VS"]], row[_F["BLOCKS_X"]], row[_F["BLOCKS_Y"]] = it.hs, it.vs, it.blocks_x, it.blocks_y
-                coef_at += 128 * blocks[i]
-                plane_bytes = int(h.madtp_jpeg_plane_bytes(it.components, it.hs, it.vs, it.blocks_x, it.blocks_y))
-                plane_at, plane_sum = int(row[_F["PLANES"]]) + plane_bytes, plane_sum + plane_bytes
-            out_at = _align(tb + qb + coef_at, 256)
-            for i, (kind, it, _) in enumerate(kinds):
-                if kind == "raw":
-                    table[i, _F["OUT"]] = out_at + raw_bytes
-                    raw_bytes += _align(it.size, 16)
-            copy_bytes = out_at + raw_bytes if raw_bytes else tb + qb + coef_at
-            total = out_at + raw_bytes
-            n_idct, n_rgb = 0, 0
-            for i, (kind, it, _) in enumerate(kinds):
-                row = table[i]
-                # every row has a place in both grids (the search wants non-decreasing prefixes); a decoded image has no workgroup
-                row[_F["FIRST_IDCT"]], row[_F["FIRST_RGB"]] = n_idct, n_rgb
-                if kind == "coef":
-                    row[_F["OUT"]] = total
-                    total += _align(int(h.madtp_jpeg_out_bytes(it.width, it.height)), 16)
-                    n_idct += h.madtp_jpeg_idct_groups(blocks[i])
-                    n_rgb += h.madtp_jpeg_rgb_groups(it.width, it.height)
-            turn, stage = self._staging(copy_bytes)
-            view = stage.numpy()
-            dev_table = table.copy()
-            dev_table[:, _F["OUT"]] -= out_at  # `out` of the launches is the packed buffer past the staged part
-            view[:tb] = dev_table.view(np.uint8).reshape(-1)
-            qview = view[tb:tb + qb].view(np.uint16).reshape(B, 3, 8, 8)
-            base = tb + qb
+                files[i] = _byte_array(it, f"image {i}")
+                it = EntropyImage(*_inspect(files[i], f"image {i}"), None)
+            claimed = None if it.coef is None else int(it.coef.shape[0]) if tuple(it.coef.shape[1:]) == (64,) else -1
+            facts.append(("coded", it, claimed, None))
+        self._need_gpu("tests/jpeg_ref.py restates the arithmetic for CPU checking.")
+        plan = plan_batch(facts)
 
-            def fill(i):
-                kind, it, buf = kinds[i]
-                if kind == "raw":
-                    o = int(table[i, _F["OUT"]])
-                    np.copyto(view[o:o + it.size].reshape(it.shape), it)
-                    return
-                q = np.asarray(it.qtables.numpy() if torch.is_tensor(it.qtables) else it.qtables, dtype=np.uint16)
-                qview[i] = q.reshape(3, 8, 8).transpose(0, 2, 1)  # column-major, as the coefficients are
-                o = base + int(table[i, _F["COEF"]])
-                n = 128 * blocks[i]
-                if buf is None:
-                    np.copyto(view[o:o + n].view(np.int16).reshape(-1, 64), it.coef.numpy())
+        def fill(view, stage):
+            def one(job):
+                i, blocks = job
+                o = plan.coef_at + int(plan.table[i, _F["COEF"]])
+                if i in files:  # straight into the pinned buffer
+                    buf = files[i]
+                    _raise(h.madtp_jpeg_entropy_decode(buf.ctypes.data, buf.size, stage.data_ptr() + o, 64 * blocks), f"image {i}")
                 else:
-                    _raise(h.madtp_jpeg_entropy_decode(buf.ctypes.data, buf.size, stage.data_ptr() + o, n // 2), f"image {i}")
+                    np.copyto(view[o:o + 128 * blocks].view(np.int16).reshape(-1, 64), facts[i][1].coef.numpy())
 
-            self._map(fill, list(range(B)))  # (an exception of any item surfaces here, before the copy and the launches)
-            packed = torch.empty(max(total, 1), dtype=torch.uint8, device=device)
-            packed[:copy_bytes].copy_(stage[:copy_bytes], non_blocking=True)
-            if self._events[turn] is None:
-                self._events[turn] = torch.cuda.Event()
-            self._events[turn].record()
-            planes = torch.empty(max(int(h.madtp_jpeg_workspace(B, plane_sum)), 1), dtype=torch.uint8, device=device)
-        shapes = [((it.height, it.width) if kind == "coef" else it.shape[:2], int(table[i, _F["OUT"]])) for i, (kind, it, _) in enumerate(kinds)]
-        return PreparedJpegBatch(packed, planes, tb, qb, out_at, B, n_idct, n_rgb, shapes)
+            self._pool.map(one, list(zip(plan.coded, plan.blocks)))
+
+        return PreparedJpegBatch(*self._send(plan, decoded, fill), plan)
 
     def launches(self, batch):
         """-> [(entry point, launch(stream) -> code)] of a prepared batch, in order (tools time them one by one)"""
-        h = lib()
-        p = batch.packed.data_ptr()
-        todo = []
-        if batch.n_idct:
-            todo.append(("madtp_jpeg_idct_batch", lambda stream: h.madtp_jpeg_idct_batch(
-                p + batch.table_bytes + batch.qtable_bytes, p + batch.table_bytes, p, batch.planes.data_ptr(), batch.B, batch.n_idct, stream)))
-            todo.append(("madtp_jpeg_rgb_batch", lambda stream: h.madtp_jpeg_rgb_batch(
-                batch.planes.data_ptr(), p, p + batch.out_at, batch.B, batch.n_rgb, stream)))
-        return todo
+        return self._pixel_launches(batch)
 
     def run(self, batch):
         """the two launches on the current stream -> list of uint8 [h,w,3] views of the batch's packed buffer"""
         with torch.cuda.device(batch.packed.device):
             for name, launch in self.launches(batch):
                 hip._check(launch(torch.cuda.current_stream().cuda_stream), name)
-        return [batch.packed[o:o + 3 * hh * ww].view(hh, ww, 3) for (hh, ww), o in batch.shapes]
-
-
-# what prepare() leaves on the device: table, quantisation tables, coefficients and decoded pass-through images in one buffer (the
-# decoded outputs follow in the same buffer), the plane scratch, and the launches' host arguments
-PreparedJpegBatch = collections.namedtuple("PreparedJpegBatch", "packed planes table_bytes qtable_bytes out_at B n_idct n_rgb shapes")
+        return self._images(batch)
 
 
 # ---- the data loader's side ------------------------------------------------------------------------------------------------------
@@ -333,16 +382,12 @@ def _factory_key(then):
     return id(then)
 
 
-def _is_item(x):
-    return isinstance(x, EntropyImage) or preprocess._is_raw(x)
-
-
-class RawJpegBatch:
-    """The images of a batch as jpeg.read() made them in the workers (EntropyImages, and raw uint8 [h,w,3] tensors of files that
-    went to Pillow).  to(device) decodes them and hands the device images to `then`: an ImagePipeline / TrainTransform instance, or
-    a factory of one called as then(device=device) (functools.partial(preprocess.ImagePipeline, 384): what a loader with worker
-    processes needs, since an instance does not pickle) - so a driver's `image = image.to(device, non_blocking=True)` works
-    unchanged."""
+class _DecodedBatch:
+    """The images of a batch as a read() made them in the workers.  to(device) decodes them with one `decoder` per device and hands
+    the device images to `then`: an ImagePipeline / TrainTransform instance, or a factory of one called as then(device=device)
+    (functools.partial(preprocess.ImagePipeline, 384): what a loader with worker processes needs, since an instance does not pickle)
+    - so a driver's `image = image.to(device, non_blocking=True)` works unchanged."""
+    decoder = item = None  # the decoder's class and the class of a coded item: a subclass names them
 
     def __init__(self, items, then):
         self.items, self.then = list(items), then
@@ -350,29 +395,33 @@ class RawJpegBatch:
     def __len__(self):
         return len(self.items)
 
+    @classmethod
+    def collate(cls, samples, then):
+        is_item = lambda x: isinstance(x, cls.item) or preprocess._is_raw(x)
+        return preprocess.collate_with(samples, is_item, lambda col: cls(col, then))
+
     def to(self, device, non_blocking=False, **_):
         device = torch.device(device)
-        if str(device) not in _decoders:
-            _decoders[str(device)] = JpegDecoder(device)
+        if (self.decoder, str(device)) not in _decoders:
+            _decoders[self.decoder, str(device)] = self.decoder(device)
         then = self.then
         if not hasattr(then, "prepare") and not hasattr(then, "last_plan"):  # a factory, not an instance
             key = (_factory_key(then), str(device))
             if key not in _thens:
                 _thens[key] = (then, then(device=device))  # (the factory is kept: an id in the key stays taken)
             then = _thens[key][1]
-        return then(_decoders[str(device)](self.items))
+        return then(_decoders[self.decoder, str(device)](self.items))
 
     def cuda(self, device=None, non_blocking=False):
         return self.to("cuda" if device is None else device)
 
 
+class RawJpegBatch(_DecodedBatch):
+    """_DecodedBatch of what jpeg.read() makes: EntropyImages, and raw uint8 [h,w,3] tensors of files that went to Pillow"""
+    decoder, item = JpegDecoder, EntropyImage
+
+
 def collate(samples, then):
     """collate_fn (bind `then` with functools.partial): the EntropyImages / raw images of the samples become one RawJpegBatch,
     everything else goes through torch's default_collate.  Samples are such images or tuples / lists that hold one."""
-    from torch.utils.data import default_collate
-    first = samples[0]
-    if _is_item(first):
-        return RawJpegBatch(samples, then)
-    if isinstance(first, (tuple, list)):
-        return [RawJpegBatch(col, then) if _is_item(col[0]) else default_collate(list(col)) for col in zip(*samples)]
-    return default_collate(samples)
+    return RawJpegBatch.collate(samples, then)

@@ -14,43 +14,24 @@ The accepted files, the refusals (jpeg.UnsupportedJpeg) and the malformed stream
 jpeg.py's.  A header-level refusal raises before any launch; a malformed scan is found by the kernel and raises after the wait for
 the batch's status words.  There is no fallback: without a GPU the decoder raises."""
 import collections
-import concurrent.futures
 import os
-import threading
 
 import numpy as np
 import torch
 
-from . import abi, hip, jpeg, preprocess
+from . import abi, hip, jpeg
+from .staging import MAX_WORKERS
 
 HEADER = os.path.join(os.path.dirname(abi.HEADER), "madtp_jhuff.h")
-with open(HEADER) as _f:
-    SIGNATURES, _, DEFINES = abi.parse(_f.read())  # the one declaration of the madtp_jhuff_* entry points
-SIGNATURES = {k: v for k, v in SIGNATURES.items() if k.startswith("madtp_jhuff_")}
+# the one declaration of the madtp_jhuff_* entry points; lib() sets them on jpeg.lib()'s handle: the IDCT and colour launches are its
+SIGNATURES, DEFINES, lib = abi.bind("madtp_jhuff.h", "madtp_jhuff_abi_version", prefix="madtp_jhuff_", needs=jpeg.lib)
 ABI_VERSION = DEFINES["MADTP_JHUFF_ABI_VERSION"]
 FIELDS, STATUS_FIELDS, RECORD_BYTES = DEFINES["MADTP_JHUFF_FIELDS"], DEFINES["MADTP_JHUFF_STATUS_FIELDS"], DEFINES["MADTP_JHUFF_RECORD_BYTES"]
 LANES, MAX_BYTES = DEFINES["MADTP_JHUFF_LANES"], DEFINES["MADTP_JHUFF_MAX_BYTES"]
 _F = {k[len("MADTP_JHUFF_F_"):]: v for k, v in DEFINES.items() if k.startswith("MADTP_JHUFF_F_")}
 _S = {k[len("MADTP_JHUFF_S_"):]: v for k, v in DEFINES.items() if k.startswith("MADTP_JHUFF_S_")}
 _I, _JF = jpeg._I, jpeg._F
-MAX_WORKERS = 16
-
-_bound = False
-
-
-def lib():
-    """hip.load()'s handle with the madtp_jhuff_* (and madtp_jpeg_*) signatures set on it (no GPU needed)"""
-    global _bound
-    h = jpeg.lib()
-    if not _bound:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(h, name)  # AttributeError => header/library mismatch
-            fn.restype = res
-            fn.argtypes = args
-        if h.madtp_jhuff_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"libmadtp_hip jhuff ABI {h.madtp_jhuff_abi_version()} != binding {ABI_VERSION}; rebuild")
-        _bound = True
-    return h
+_SCANS = jpeg.ScanFormat(_F, FIELDS, RECORD_BYTES, MAX_BYTES)
 
 
 def _check_subseq(subseq_bytes):
@@ -69,9 +50,7 @@ class ScanImage:
 
     def __init__(self, data, info, qtables, tables, scan_begin):
         self.data = data
-        self.width, self.height, self.components = int(info[_I["WIDTH"]]), int(info[_I["HEIGHT"]]), int(info[_I["COMPONENTS"]])
-        self.hs, self.vs = int(info[_I["HS"]]), int(info[_I["VS"]])
-        self.blocks_x, self.blocks_y, self.restart_interval = int(info[_I["BLOCKS_X"]]), int(info[_I["BLOCKS_Y"]]), int(info[_I["RESTART"]])
+        jpeg._set_header(self, info)
         self.blocks = int(info[_I["BLOCKS"]])
         self.qtables, self.tables, self.scan_begin = qtables, tables, int(scan_begin)
 
@@ -101,17 +80,7 @@ def read(source, other="raise"):
     """a path or bytes -> ScanImage: the dataset's replacement for Image.open(path).convert('RGB').  other="pil": a file this
     decoder REFUSES by its header (UnsupportedJpeg) is decoded by Pillow to preprocess.raw_image()'s uint8 [h,w,3] tensor, which the
     decoder passes through; a corrupt header raises either way, a corrupt scan raises when the batch is decoded."""
-    if other not in ("raise", "pil"):
-        raise ValueError(f"read: other={other!r} is not 'raise' or 'pil'")
-    buf = jpeg._byte_array(source, "read")
-    try:
-        return prepare_scan(buf, str(source) if isinstance(source, (str, os.PathLike)) else "read")
-    except jpeg.UnsupportedJpeg:
-        if other != "pil":
-            raise
-    import io
-    from PIL import Image
-    return preprocess.raw_image(Image.open(io.BytesIO(buf.tobytes())))
+    return jpeg._read_with(prepare_scan, source, other)
 
 
 def decode_host(data, subseq_bytes=None):
@@ -130,17 +99,13 @@ def decode_host(data, subseq_bytes=None):
     return rc, coef if rc == 0 else None, status
 
 
-def _align(n, a):
-    return (n + a - 1) // a * a
+class PreparedDeviceBatch(jpeg._Prepared, collections.namedtuple("PreparedDeviceBatch", "packed planes plan status subseq_bytes")):
+    """what prepare() leaves on the device: the packed buffer of the plan (jpeg.JpegPlan), the plane scratch, the plan, the status
+    words of the decode kernel and the subsequence size of its launch"""
+    __slots__ = ()
 
 
-# what prepare() leaves on the device: one buffer [tables and files as staged | coefficients | decoded images], the plane scratch,
-# the status words, and the launches' host arguments
-PreparedDeviceBatch = collections.namedtuple(
-    "PreparedDeviceBatch", "packed planes status jtable_at qtable_at htable_at coef_at out_at B coded blocks n_idct n_rgb shapes copy_bytes subseq_bytes")
-
-
-class DeviceJpegDecoder:
+class DeviceJpegDecoder(jpeg._BatchDecoder):
     """JPEG files -> uint8 [h,w,3] tensors on `device`, views of one packed buffer: one copy of the compressed bytes and three
     launches per batch (madtp_jhuff_decode_batch, madtp_jpeg_idct_batch, madtp_jpeg_rgb_batch).
 
@@ -152,138 +117,41 @@ class DeviceJpegDecoder:
     subseq_bytes: None for the library's choice per image, else the subsequence size of every image (tests force small ones)."""
 
     def __init__(self, device="cuda", workers=8, subseq_bytes=None):
-        self.device = torch.device(device)
-        self.workers = max(1, min(int(workers), MAX_WORKERS))
+        super().__init__(device, workers, "madtp-jhuff")
         self.subseq_bytes = _check_subseq(subseq_bytes)
-        self._pool = None
-        self._stage = [None, None]
-        self._events = [None, None]
-        self._turn = 0
         self._side = None
         self._host_status = None
-        self._lock = threading.Lock()
         self.last_status = None  # int32 [coded images, STATUS_FIELDS] of the last batch (numpy), for tools and tests
-
-    def _staging(self, nbytes):
-        i = self._turn
-        self._turn ^= 1
-        if self._events[i] is not None:
-            self._events[i].synchronize()
-        if self._stage[i] is None or self._stage[i].numel() < nbytes:
-            self._stage[i] = torch.empty(max(nbytes, 1 << 20) * 5 // 4, dtype=torch.uint8, pin_memory=True)
-        return i, self._stage[i]
-
-    def _map(self, fn, jobs):
-        if self.workers == 1 or len(jobs) < 2:
-            return [fn(j) for j in jobs]
-        if self._pool is None:
-            self._pool = concurrent.futures.ThreadPoolExecutor(self.workers, thread_name_prefix="madtp-jhuff")
-        futures = [self._pool.submit(fn, j) for j in jobs]
-        concurrent.futures.wait(futures)
-        return [f.result() for f in futures]
-
-    def __call__(self, items):
-        return self.run(self.prepare(items))
 
     def prepare(self, items):
         """the header checks, the packing and the copy -> PreparedDeviceBatch for run()"""
         items = list(items)
-        B = len(items)
-        if B < 1:
+        if len(items) < 1:
             raise ValueError("DeviceJpegDecoder: an empty batch")
-        h = lib()
+        lib()  # (bound before the pool's threads call it)
 
         def parse(i):
             it = items[i]
             if isinstance(it, ScanImage):
-                return ("scan", it)
-            if (torch.is_tensor(it) or isinstance(it, np.ndarray)) and it.ndim == 3:
-                host, _ = preprocess._as_uint8_hw3(it, i)
-                if host is None:
-                    raise ValueError(f"image {i}: a decoded image must be a host array (device images need no decoder)")
-                return ("raw", host)
-            return ("scan", prepare_scan(jpeg._byte_array(it, f"image {i}"), f"image {i}"))
+                return it
+            host = self._decoded(it, i)
+            return host if host is not None else prepare_scan(jpeg._byte_array(it, f"image {i}"), f"image {i}")
 
-        kinds = self._map(parse, list(range(B)))  # (a header this decoder refuses raises here, before any launch)
-        if self.device.type != "cuda" or not torch.cuda.is_available():
-            raise RuntimeError(f"DeviceJpegDecoder on {self.device}: madtp_amd runs only on an MI355X through the HIP kernels (no CPU / "
-                               "eager fallback).  jpeg_device.decode_host runs the kernel's passes on the host for CPU checking.")
-        with self._lock, torch.cuda.device(self.device if self.device.index is not None else torch.cuda.current_device()):
-            device = torch.device("cuda", torch.cuda.current_device())
-            coded = [i for i, (kind, _) in enumerate(kinds) if kind == "scan"]
-            jtable = np.zeros((B, jpeg.FIELDS), dtype=np.int64)        # rows of the IDCT and colour kernels: every image
-            htable = np.zeros((max(len(coded), 1), FIELDS), dtype=np.int64)  # rows of the decode kernel: the coded images
-            jtable_at, qtable_at = 0, jtable.nbytes
-            htable_at = qtable_at + B * 384
-            at = _align(htable_at + htable.nbytes, 16)
-            coef_bytes, plane_at, plane_sum, n_idct, n_rgb = 0, 0, 0, 0, 0
-            for n, i in enumerate(coded):
-                it = kinds[i][1]
-                blocks = int(h.madtp_jpeg_blocks(it.components, it.hs, it.vs, it.blocks_x, it.blocks_y))
-                if blocks < 1 or blocks != it.blocks or not (1 <= it.width <= 8 * it.blocks_x and 1 <= it.height <= 8 * it.blocks_y) or \
-                        not 0 <= it.scan_begin <= it.data.size <= MAX_BYTES or it.tables.size != RECORD_BYTES:
-                    raise ValueError(f"image {i}: a ScanImage whose fields contradict each other")
-                row = htable[n]
-                row[_F["RECORD"]], at = at, at + RECORD_BYTES
-                row[_F["FILE"]], at = at, _align(at + it.data.size, 16)
-                row[_F["SIZE"]], row[_F["SCAN"]], row[_F["COEF"]] = it.data.size, it.scan_begin, coef_bytes
-                row[_F["COMPONENTS"]], row[_F["HS"]], row[_F["VS"]] = it.components, it.hs, it.vs
-                row[_F["BLOCKS_X"]], row[_F["BLOCKS_Y"]], row[_F["RESTART"]] = it.blocks_x, it.blocks_y, it.restart_interval
-                jrow = jtable[i]
-                jrow[_JF["COEF"]], jrow[_JF["QTABLE"]], jrow[_JF["PLANES"]] = coef_bytes, i * 384, _align(plane_at, 256)
-                jrow[_JF["W"]], jrow[_JF["H"]], jrow[_JF["COMPONENTS"]] = it.width, it.height, it.components
-                jrow[_JF["HS"]], jrow[_JF["VS"]], jrow[_JF["BLOCKS_X"]], jrow[_JF["BLOCKS_Y"]] = it.hs, it.vs, it.blocks_x, it.blocks_y
-                coef_bytes += 128 * blocks
-                plane_bytes = 64 * blocks
-                plane_at, plane_sum = int(jrow[_JF["PLANES"]]) + plane_bytes, plane_sum + plane_bytes
-            raw_at = _align(at, 16)
-            raw_bytes = 0
-            for i, (kind, it) in enumerate(kinds):
-                if kind == "raw":
-                    jtable[i, _JF["OUT"]] = raw_bytes
-                    raw_bytes += _align(it.size, 16)
-            copy_bytes = raw_at + raw_bytes
-            coef_at = _align(copy_bytes, 256)
-            out_at = _align(coef_at + coef_bytes, 256)
-            total = 0
-            shapes = []
-            for i, (kind, it) in enumerate(kinds):
-                jrow = jtable[i]
-                jrow[_JF["FIRST_IDCT"]], jrow[_JF["FIRST_RGB"]] = n_idct, n_rgb
-                if kind == "scan":
-                    jrow[_JF["OUT"]] = total
-                    shapes.append(((it.height, it.width), out_at + total))
-                    total += _align(int(h.madtp_jpeg_out_bytes(it.width, it.height)), 16)
-                    n_idct += h.madtp_jpeg_idct_groups(it.blocks)
-                    n_rgb += h.madtp_jpeg_rgb_groups(it.width, it.height)
-                else:
-                    shapes.append((it.shape[:2], raw_at + int(jrow[_JF["OUT"]])))
-            turn, stage = self._staging(copy_bytes)
-            view = stage.numpy()
-            view[jtable_at:jtable_at + jtable.nbytes] = jtable.view(np.uint8).reshape(-1)
-            view[htable_at:htable_at + htable.nbytes] = htable.view(np.uint8).reshape(-1)
-            qview = view[qtable_at:qtable_at + B * 384].view(np.uint16).reshape(B, 3, 8, 8)
-            qview[:] = 0
-            for n, i in enumerate(coded):
-                it = kinds[i][1]
-                qview[i] = np.asarray(it.qtables, dtype=np.uint16).reshape(3, 8, 8).transpose(0, 2, 1)  # column-major, as the coefficients
-                o = int(htable[n, _F["RECORD"]])
-                view[o:o + RECORD_BYTES] = it.tables
-                o = int(htable[n, _F["FILE"]])
-                view[o:o + it.data.size] = it.data
-            for i, (kind, it) in enumerate(kinds):
-                if kind == "raw":
-                    o = raw_at + int(jtable[i, _JF["OUT"]])
-                    np.copyto(view[o:o + it.size].reshape(it.shape), it)
-            packed = torch.empty(max(out_at + total, 1), dtype=torch.uint8, device=device)
-            packed[:copy_bytes].copy_(stage[:copy_bytes], non_blocking=True)
-            if self._events[turn] is None:
-                self._events[turn] = torch.cuda.Event()
-            self._events[turn].record()
-            planes = torch.empty(max(int(h.madtp_jpeg_workspace(B, plane_sum)), 1), dtype=torch.uint8, device=device)
-            status = torch.empty(max(len(coded), 1), STATUS_FIELDS, dtype=torch.int32, device=device)
-        return PreparedDeviceBatch(packed, planes, status, jtable_at, qtable_at, htable_at, coef_at, out_at, B, coded,
-                                   [kinds[i][1].blocks for i in coded], n_idct, n_rgb, shapes, copy_bytes, self.subseq_bytes)
+        parsed = self._pool.map(parse, list(range(len(items))))  # (a header this decoder refuses raises here, before any launch)
+        self._need_gpu("jpeg_device.decode_host runs the kernel's passes on the host for CPU checking.")
+        decoded = {i: it for i, it in enumerate(parsed) if not isinstance(it, ScanImage)}
+        plan = jpeg.plan_batch([("raw", it.shape) if i in decoded else ("coded", it, it.blocks, (it.data.size, it.scan_begin, it.tables.size))
+                                for i, it in enumerate(parsed)], _SCANS)
+
+        def fill(view, stage):
+            for row, i in zip(plan.htable, plan.coded):
+                it, record, file = parsed[i], int(row[_F["RECORD"]]), int(row[_F["FILE"]])
+                view[record:record + RECORD_BYTES] = it.tables
+                view[file:file + it.data.size] = it.data
+
+        packed, planes = self._send(plan, decoded, fill)
+        status = torch.empty(max(len(plan.coded), 1), STATUS_FIELDS, dtype=torch.int32, device=packed.device)
+        return PreparedDeviceBatch(packed, planes, plan, status, self.subseq_bytes)
 
     @staticmethod
     def coefficients(batch):
@@ -297,17 +165,12 @@ class DeviceJpegDecoder:
     def launches(self, batch):
         """-> [(entry point, launch(stream) -> code)] of a prepared batch, in order (tools time them one by one)"""
         h = lib()
-        p = batch.packed.data_ptr()
-        todo = []
-        if batch.coded:
-            todo.append(("madtp_jhuff_decode_batch", lambda stream: h.madtp_jhuff_decode_batch(
-                p, p + batch.htable_at, p + batch.coef_at, batch.status.data_ptr(), len(batch.coded), batch.subseq_bytes, stream)))
-            # (a raw image's OUT row is never read: it has no workgroup in either grid)
-            todo.append(("madtp_jpeg_idct_batch", lambda stream: h.madtp_jpeg_idct_batch(
-                p + batch.coef_at, p + batch.qtable_at, p + batch.jtable_at, batch.planes.data_ptr(), batch.B, batch.n_idct, stream)))
-            todo.append(("madtp_jpeg_rgb_batch", lambda stream: h.madtp_jpeg_rgb_batch(
-                batch.planes.data_ptr(), p + batch.jtable_at, p + batch.out_at, batch.B, batch.n_rgb, stream)))
-        return todo
+        p, plan = batch.packed.data_ptr(), batch.plan
+        if not plan.coded:
+            return []
+        return [("madtp_jhuff_decode_batch", lambda stream: h.madtp_jhuff_decode_batch(
+            p, p + plan.htable_at, p + plan.coef_at, batch.status.data_ptr(), len(plan.coded), batch.subseq_bytes, stream))] + \
+            self._pixel_launches(batch)
 
     def run(self, batch):
         """the three launches on the current stream and the wait for the status words -> list of uint8 [h,w,3] views of the batch's
@@ -341,52 +204,17 @@ class DeviceJpegDecoder:
                         jpeg._raise(code, f"image {i}")
                     elif code != 0:
                         hip._check(code, f"madtp_jhuff_decode_batch (image {i})")
-        return [batch.packed[o:o + 3 * hh * ww].view(hh, ww, 3) for (hh, ww), o in batch.shapes]
+        return self._images(batch)
 
 
 # ---- the data loader's side ------------------------------------------------------------------------------------------------------
-_decoders = {}
-_thens = {}
-
-
-def _is_item(x):
-    return isinstance(x, ScanImage) or preprocess._is_raw(x)
-
-
-class RawJpegDeviceBatch:
-    """The images of a batch as jpeg_device.read() made them in the workers (ScanImages, and raw uint8 [h,w,3] tensors of files
-    that went to Pillow).  to(device) decodes them on the device and hands the images to `then`: an ImagePipeline / TrainTransform
-    instance, or a factory of one called as then(device=device) - jpeg.RawJpegBatch's contract."""
-
-    def __init__(self, items, then):
-        self.items, self.then = list(items), then
-
-    def __len__(self):
-        return len(self.items)
-
-    def to(self, device, non_blocking=False, **_):
-        device = torch.device(device)
-        if str(device) not in _decoders:
-            _decoders[str(device)] = DeviceJpegDecoder(device)
-        then = self.then
-        if not hasattr(then, "prepare") and not hasattr(then, "last_plan"):  # a factory, not an instance
-            key = (jpeg._factory_key(then), str(device))
-            if key not in _thens:
-                _thens[key] = (then, then(device=device))
-            then = _thens[key][1]
-        return then(_decoders[str(device)](self.items))
-
-    def cuda(self, device=None, non_blocking=False):
-        return self.to("cuda" if device is None else device)
+class RawJpegDeviceBatch(jpeg._DecodedBatch):
+    """jpeg._DecodedBatch of what jpeg_device.read() makes (ScanImages, and raw uint8 [h,w,3] tensors of files that went to
+    Pillow), decoded on the device: jpeg.RawJpegBatch's contract"""
+    decoder, item = DeviceJpegDecoder, ScanImage
 
 
 def collate(samples, then):
     """collate_fn (bind `then` with functools.partial): the ScanImages / raw images of the samples become one RawJpegDeviceBatch,
     everything else goes through torch's default_collate.  Samples are such images or tuples / lists that hold one."""
-    from torch.utils.data import default_collate
-    first = samples[0]
-    if _is_item(first):
-        return RawJpegDeviceBatch(samples, then)
-    if isinstance(first, (tuple, list)):
-        return [RawJpegDeviceBatch(col, then) if _is_item(col[0]) else default_collate(list(col)) for col in zip(*samples)]
-    return default_collate(samples)
+    return RawJpegDeviceBatch.collate(samples, then)

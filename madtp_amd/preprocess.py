@@ -20,11 +20,11 @@ import threading
 import numpy as np
 import torch
 
-from . import abi, hip
+from . import abi, hip, staging
 
 HEADER = os.path.join(os.path.dirname(abi.HEADER), "madtp_image.h")
-with open(HEADER) as _f:
-    SIGNATURES, _, DEFINES = abi.parse(_f.read())  # the one declaration of the image entry points, as abi.SIGNATURES is of madtp_hip.h
+# the one declaration of the image entry points, as abi.SIGNATURES is of madtp_hip.h; lib() is hip.load()'s handle with them set
+SIGNATURES, DEFINES, lib = abi.bind("madtp_image.h", "madtp_image_abi_version")
 ABI_VERSION = DEFINES["MADTP_IMAGE_ABI_VERSION"]
 FIELDS, MAX_KSIZE = DEFINES["MADTP_IMAGE_FIELDS"], DEFINES["MADTP_IMAGE_MAX_KSIZE"]
 _F = {k[len("MADTP_IMAGE_F_"):]: v for k, v in DEFINES.items() if k.startswith("MADTP_IMAGE_F_")}
@@ -33,23 +33,6 @@ MAX_SIDE = 8192
 # the constants of both reference families (data/__init__.py:20, clip/clip.py:87)
 MEAN = (0.48145466, 0.4578275, 0.40821073)
 STD = (0.26862954, 0.26130258, 0.27577711)
-
-_bound = False
-
-
-def lib():
-    """hip.load()'s handle with the madtp_image_* signatures set on it (no GPU needed)"""
-    global _bound
-    h = hip.load()
-    if not _bound:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(h, name)  # AttributeError => header/library mismatch
-            fn.restype = res
-            fn.argtypes = args
-        if h.madtp_image_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"libmadtp_hip image ABI {h.madtp_image_abi_version()} != binding {ABI_VERSION}; rebuild")
-        _bound = True
-    return h
 
 
 # ---- Pillow's coefficient tables (Resample.c precompute_coeffs + normalize_coeffs_8bpc) -----------------------------------------
@@ -185,9 +168,7 @@ class ImagePipeline:
         self.device = torch.device(device)
         self.table = normalize_table(mean, std)
         self._lut = None
-        self._stage = [None, None]
-        self._events = [None, None]
-        self._turn = 0
+        self._ring = staging.StagingRing()
         self._lock = threading.Lock()
 
     def _axes(self, w, h, index):
@@ -203,16 +184,6 @@ class ImagePipeline:
                 raise ValueError(f"image {index}: {w} x {h} -> {n_out} pixels is a downscale ratio of {n_in / n_out:.2f}, beyond "
                                  f"the supported 16")
         return ax, ay
-
-    def _staging(self, nbytes):
-        """the next pinned buffer (as a uint8 tensor of at least nbytes), once the copy that last read it has finished"""
-        i = self._turn
-        self._turn ^= 1
-        if self._events[i] is not None:
-            self._events[i].synchronize()
-        if self._stage[i] is None or self._stage[i].numel() < nbytes:
-            self._stage[i] = torch.empty(max(nbytes, 1 << 20) * 5 // 4, dtype=torch.uint8, pin_memory=True)
-        return i, self._stage[i]
 
     def __call__(self, images, boxes=None, flips=None, out=None):
         """images: list of uint8 [h,w,3] numpy arrays, CPU tensors, PIL RGB images, or uint8 tensors on the device (all of them
@@ -274,7 +245,7 @@ class ImagePipeline:
                     raise ValueError(f"image {i}: no tile height fits a row table of {int(row[_F['KSY']])} coefficients")
                 row[_F["FLIP"]], row[_F["TILE_H"]], row[_F["FIRST"]] = int(bool(flips[i])), tile_h, n_blocks
                 n_blocks += h.madtp_image_blocks(self.Sh, self.Sw, tile_h)
-            turn, stage = self._staging(tb + (0 if all(on_device) else offset))
+            turn, stage = self._ring.acquire(tb + (0 if all(on_device) else offset))
             view = stage.numpy()
             view[:tb] = table.view(np.uint8).reshape(-1)
             packed = torch.empty(tb + offset, dtype=torch.uint8, device=device)
@@ -286,9 +257,7 @@ class ImagePipeline:
                     o = tb + int(table[i, _F["OFFSET"]])
                     np.copyto(view[o:o + 3 * (r - l) * (d - u)].reshape(d - u, r - l, 3), host[u:d, l:r])
                 packed.copy_(stage[:tb + offset], non_blocking=True)
-            if self._events[turn] is None:
-                self._events[turn] = torch.cuda.Event()
-            self._events[turn].record()
+            self._ring.sent(turn)
         return PreparedBatch(packed, tb, B, n_blocks, max_ksize, self._lut)
 
     def run(self, batch, out=None):
@@ -342,13 +311,19 @@ def _is_raw(x):
     return torch.is_tensor(x) and x.dtype == torch.uint8 and x.dim() == 3 and x.shape[2] == 3
 
 
+def collate_with(samples, is_item, make):
+    """the body of every collate_fn of the image input path: the columns of the samples whose entries are items (is_item) become
+    make(column), everything else goes through torch's default_collate.  Samples are items or tuples / lists that hold one."""
+    from torch.utils.data import default_collate
+    first = samples[0]
+    if is_item(first):
+        return make(samples)
+    if isinstance(first, (tuple, list)):
+        return [make(col) if is_item(col[0]) else default_collate(list(col)) for col in zip(*samples)]
+    return default_collate(samples)
+
+
 def collate(samples, size, mode="stretch", mean=MEAN, std=STD):
     """collate_fn (bind `size` with functools.partial): the raw uint8 [h,w,3] images of the samples become one RawImageBatch,
     everything else goes through torch's default_collate.  Samples are raw images or tuples / lists that hold one."""
-    from torch.utils.data import default_collate
-    first = samples[0]
-    if _is_raw(first):
-        return RawImageBatch(samples, size, mode, mean, std)
-    if isinstance(first, (tuple, list)):
-        return [RawImageBatch(col, size, mode, mean, std) if _is_raw(col[0]) else default_collate(list(col)) for col in zip(*samples)]
-    return default_collate(samples)
+    return collate_with(samples, _is_raw, lambda col: RawImageBatch(col, size, mode, mean, std))

@@ -16,28 +16,10 @@ import torch
 from . import abi, hip
 
 HEADER = os.path.join(os.path.dirname(abi.HEADER), "madtp_search.h")
-with open(HEADER) as _f:
-    SIGNATURES, _, DEFINES = abi.parse(_f.read())  # the one declaration of the search entry points
+# the one declaration of the search entry points; lib() is hip.load()'s handle with them set on it (no GPU needed)
+SIGNATURES, DEFINES, lib = abi.bind("madtp_search.h", "madtp_search_abi_version")
 ABI_VERSION = DEFINES["MADTP_SEARCH_ABI_VERSION"]
 MAX_K = DEFINES["MADTP_TOPK_MAX_K"]
-
-_bound = False
-
-
-def lib():
-    """hip.load()'s handle with the signatures of madtp_search.h set on it (no GPU needed)"""
-    global _bound
-    h = hip.load()
-    if not _bound:
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(h, name)  # AttributeError => header/library mismatch
-            fn.restype = res
-            fn.argtypes = args
-        if h.madtp_search_abi_version() != ABI_VERSION:
-            raise RuntimeError(f"libmadtp_hip search ABI {h.madtp_search_abi_version()} != binding {ABI_VERSION}; rebuild")
-        _bound = True
-    return h
-
 
 def _check_k(k, what):
     k = int(k)

@@ -195,7 +195,7 @@ def main():
         med, lo, hi = event_ms(launch)
         lines.append(f"  {name:22s} {med:8.4f} ms  ({lo:.4f} .. {hi:.4f});  bytes it must move {moved / 1e6:.1f} MB ({what}) -> "
                      f"{moved / (med * 1e-3) / 1e12:.2f} TB/s = {100 * moved / (med * 1e-3) / HBM_PEAK:.1f} % of the 8 TB/s HBM peak")
-    lines.append(f"  host-to-device copy of the batch: {batch.out_at / 1e6:.1f} MB of tables and int16 coefficients for {3 * pixels / 1e6:.1f} MB of RGB pixels")
+    lines.append(f"  host-to-device copy of the batch: {batch.copy_bytes / 1e6:.1f} MB of tables and int16 coefficients for {3 * pixels / 1e6:.1f} MB of RGB pixels")
     lines.append("\ncompiler resource report (gfx950)")
     lines += resources()
     text = "\n".join(lines) + "\n"

@@ -141,7 +141,7 @@ def main():
         S = jpeg_device._S
         host_batch = jpeg.JpegDecoder(device, workers=8).prepare(data)
         lines.append(f"bytes copied to the device per batch: device leg {batch.copy_bytes / 1e6:.2f} MB (files {sum(map(len, data)) / 1e6:.2f} MB, "
-                     f"Huffman records {B * jpeg_device.RECORD_BYTES / 1e6:.2f} MB, tables), host leg {host_batch.out_at / 1e6:.2f} MB")
+                     f"Huffman records {B * jpeg_device.RECORD_BYTES / 1e6:.2f} MB, tables), host leg {host_batch.copy_bytes / 1e6:.2f} MB")
         lines.append("kernels alone (device events, 40 launches each)")
         for name, launch in dev.launches(batch):
             med, lo, hi = jpeg_ab.event_ms(launch)
