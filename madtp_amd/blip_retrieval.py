@@ -413,7 +413,7 @@ def all_gather_scores(score_i2t, score_t2i):
 
 @torch.no_grad()
 def evaluate(model, data_loader, device, config, temperature=0, rank=0, world_size=1, text_bs=256, kv_cache=True,
-             candidates="dense"):
+             candidates="dense", coarse=None):
     """compress_retrieval_dtp.py evaluate() :84-207 -> (score_matrix_i2t, score_matrix_t2i) as numpy arrays and the GFLOPs
     placeholder (0.0: the reference's fvcore count of the TRAINING forward is out of scope, harness.nlvr_forward_flops is
     the analytic counter of this repo).  rank / world_size select this process's row slices exactly as :158-162 / :181-183
@@ -423,10 +423,17 @@ def evaluate(model, data_loader, device, config, temperature=0, rank=0, world_si
     candidates: "dense" (the default, the reference's data flow) forms sims_matrix and takes topk(k_test) of one row per loop
     iteration; "device" takes the k_test candidates of all rows, in both directions, from two search.topk_embeds calls before the
     loops and never forms sims_matrix (its ITC term is the exact-f32 score of that kernel, its order among equal scores the one
-    of madtp_search.h)."""
+    of madtp_search.h).
+    coarse: None, or "bf16" with candidates="device": the same candidates through the certified bf16 shortlist of
+    search.topk_embeds (k_test <= 128)."""
     if candidates not in ("dense", "device"):
         raise ValueError(f"candidates = {candidates!r}: expected 'dense' or 'device'")
     k_test = config['k_test']
+    if coarse is not None:
+        from . import search
+        if candidates != "device":
+            raise ValueError(f"coarse = {coarse!r} needs candidates='device'")
+        search.check_coarse(coarse, k_test, "evaluate: k_test")
     sd = model.space_dict
     texts = data_loader.dataset.text
     num_text = len(texts)
@@ -470,8 +477,9 @@ def evaluate(model, data_loader, device, config, temperature=0, rank=0, world_si
         from . import search
         if k_test > min(n_img, num_text):  # (what topk() of the dense path refuses)
             raise RuntimeError(f"k_test = {k_test} exceeds the {n_img} images or the {num_text} texts")
-        i2t_sim, i2t_idx = search.topk_embeds(image_embeds.float(), text_embeds.float(), k_test)
-        t2i_sim, t2i_idx = search.topk_embeds(text_embeds.float(), image_embeds.float(), k_test)
+        kw = {} if coarse is None else {"coarse": coarse}
+        i2t_sim, i2t_idx = search.topk_embeds(image_embeds.float(), text_embeds.float(), k_test, **kw)
+        t2i_sim, t2i_idx = search.topk_embeds(text_embeds.float(), image_embeds.float(), k_test, **kw)
         top_i2t, top_t2i = (lambda i: (i2t_sim[i], i2t_idx[i])), (lambda i: (t2i_sim[i], t2i_idx[i]))
     else:
         sims_matrix = image_embeds @ text_embeds.t()  # :155

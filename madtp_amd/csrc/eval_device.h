@@ -23,6 +23,10 @@ struct RankArgs {
     float* score_tgt;
     int32_t* part;  // [splits, cap] counts
     int splits, tiles_per_split;
+    // the optional row map (the MAPPED kernels of search_device.h): query row p of the launch is row row_map[p] of q, and
+    // *row_count rows are listed, both read on the device
+    const int32_t* row_map = nullptr;
+    const int32_t* row_count = nullptr;
 };
 
 // The one product routine of the retrieval kernels: acc0 / acc1 = rows [r0, r0 + 16) / [r0 + 16, r0 + 32) of q against the 64 key
@@ -32,17 +36,24 @@ struct RankArgs {
 // alone, not of the column's place in a tile - so a score computed for a gathered target column and the score the counting
 // pass forms for the same key row (or a byte copy of it) are the same bits.
 // The next chunk's global loads are issued before the products of the current one.
+// MAPPED: the rows are those of the row map, nrows = *a.row_count of them (read by the caller).
+template <bool MAPPED = false>
 __device__ __forceinline__ void rank_tile_products(const RankArgs& a, int r0, const int (&krow)[4], float (*Qs)[RK_LD],
-                                                   float (*Ks)[RK_LD], f32x4& acc0, f32x4& acc1) {
+                                                   float (*Ks)[RK_LD], f32x4& acc0, f32x4& acc1, int nrows = 0) {
     const int t = threadIdx.x, w = t >> 6, c = t & 15, g = (t >> 4) & 3;
     const int sr = t >> 4, d4 = (t & 15) * 4;
     const int ndc = a.D / RK_DC;
     f32x4 qreg[2], kreg[4];
+    int qrow[2];
+    for (int i = 0; i < 2; ++i) {
+        const int row = r0 + sr + 16 * i;
+        if constexpr (MAPPED) qrow[i] = row < nrows ? a.row_map[row] : -1;
+        else qrow[i] = row < a.nq ? row : -1;
+    }
     auto fetch = [&](int dc) {
         for (int i = 0; i < 2; ++i) {
-            const int row = r0 + sr + 16 * i;
             qreg[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (row < a.nq) qreg[i] = *(const f32x4*)(a.q + (size_t)row * a.ldq + dc * RK_DC + d4);
+            if (qrow[i] >= 0) qreg[i] = *(const f32x4*)(a.q + (size_t)qrow[i] * a.ldq + dc * RK_DC + d4);
         }
         for (int i = 0; i < 4; ++i) {
             kreg[i] = f32x4{0.f, 0.f, 0.f, 0.f};

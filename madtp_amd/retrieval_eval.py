@@ -144,14 +144,15 @@ class ClipEval:
         i2t, t2i = self.ranks(txt2img, img2txt)
         return recall_metrics(i2t[0], t2i[0])
 
-    def search(self, k, direction="i2t"):
+    def search(self, k, direction="i2t", coarse=None):
         """(values f32 [n,k], indices int64 [n,k]): the k best texts of every image ("i2t") or images of every text ("t2i"),
-        best first, in the order ranks() counts in (search.topk_embeds); no similarity matrix is formed."""
+        best first, in the order ranks() counts in (search.topk_embeds); no similarity matrix is formed.  coarse="bf16": the
+        same answer through the certified bf16 shortlist (k <= 128)."""
         from . import search
         if direction not in ("i2t", "t2i"):
             raise ValueError(f"direction = {direction!r}: expected 'i2t' or 't2i'")
         q, keys = (self.image_embeds, self.text_embeds) if direction == "i2t" else (self.text_embeds, self.image_embeds)
-        return search.topk_embeds(q, keys, k)
+        return search.topk_embeds(q, keys, k) if coarse is None else search.topk_embeds(q, keys, k, coarse=coarse)
 
     def score_matrices(self):
         """the reference's return value: (sims, sims.T, GFLOPs) with the matrices as numpy arrays"""

@@ -15,7 +15,19 @@ Flickr 1000 x 5000 at D 256 / k 128.
 Timing: device events around each leg; the legs alternate inside every round, leg A runs once per round and the others --iters
 times; each figure is the median over the rounds of the per-round median, with the min and max.  Peak memory: the allocator's
 peak above what is live before the leg (the embeddings).  The kernel figures (registers, LDS, waves) are the compiler's, copied
-here from -Rpass-analysis=kernel-resource-usage: see KERNELS."""
+here from -Rpass-analysis=kernel-resource-usage: see KERNELS.
+
+    python tools/topk_ab.py --coarse [--kernels-only] [--out FILE]
+
+  leg E   search.topk_embeds, the exact route (leg B above);
+  leg A'  as above;
+  leg C   search.EmbeddingIndex(keys, coarse="bf16").search: the certified bf16 shortlist over a gallery prepared once (the
+          gallery's prepare + summary are timed on their own, and so is the one-shot search.topk_embeds(coarse="bf16")).
+The outputs of legs C and E are asserted EQUAL (indices, and the values' bits), on unit-norm Gaussian rows and on "CLIP-like" rows
+(a common mean direction of weight 0.8).  Per shape: the certified share, the bytes the exact re-scoring gathers (nq m rows of
+4 D bytes) and the compiler's figures for the new kernels (COARSE_KERNELS, from tools/kernel_resources.py).  The time of each
+of the five stages comes from a kernel trace of `--coarse --kernels-only` (tools/rocpd_stats.py): that run makes ten coarse
+searches per shape and direction and nothing else."""
 import argparse
 import os
 import statistics
@@ -32,6 +44,24 @@ GAP = 2e-6
 # topk_tile_kernel<CAP>: (largest k, candidate words per row, VGPRs + AGPRs, LDS bytes per workgroup = 26 752 static + 256 CAP,
 #                         workgroups per CU by LDS (160 KiB) = waves per SIMD, 4 waves per workgroup)
 KERNELS = [(64, 128, "159 + 8", 26752 + 256 * 128, 2), (128, 256, "230 + 8", 26752 + 256 * 256, 1), (256, 512, "114 + 8", 26752 + 256 * 512, 1)]
+
+
+# search_coarse.hip: kernel, VGPRs, AGPRs, LDS bytes per workgroup (static + dynamic), waves per SIMD (registers / LDS)
+COARSE_KERNELS = [("coarse_prepare_kernel", 50, 0, 0, 8), ("ctopk_tile_kernel<128> (m 64)", 168, 0, 14464 + 256 * 128, 3),
+                  ("ctopk_tile_kernel<256> (m 128)", 228, 0, 14464 + 256 * 256, 2), ("ctopk_tile_kernel<512> (m 256)", 136, 0, 14464 + 256 * 512, 1),
+                  ("ctopk_row_kernel", 74, 0, 8464, 6), ("ctopk_compact_kernel", 18, 0, 1024, 8),
+                  ("topk_tile_kernel<128, mapped> (fallback, k <= 64)", 164, 0, 26752 + 256 * 128, 2),
+                  ("topk_tile_kernel<256, mapped> (fallback, k <= 128)", 244, 0, 26752 + 256 * 256, 1),
+                  ("topk_row_kernel<mapped>", 46, 0, 4368, 8)]
+COARSE_CASES = [(5000, 25010, 256, 128), (5000, 25010, 512, 10), (5000, 25010, 768, 10), (1000, 5000, 256, 128)]
+
+
+def clip_like(n, D, seed, dev, mean=0.8):
+    """unit rows around one common direction (seed-independent, so queries and keys share it): mean mu + sqrt(1 - mean^2) noise"""
+    mu = features(1, D, 77, dev).double()
+    noise = features(n, D, seed, dev).double()
+    x = mean * mu + (1 - mean * mean) ** 0.5 * noise
+    return (x / x.norm(dim=1, keepdim=True)).float().contiguous()
 
 
 def features(n, D, seed, dev):
@@ -140,8 +170,86 @@ def case(nq, nk, D, k, a, dev, out):
     return ok
 
 
+def equal(a, b):
+    return torch.equal(a[1], b[1]) and torch.equal(a[0].view(torch.int32), b[0].view(torch.int32))
+
+
+def coarse_case(nq, nk, D, k, family, a, dev, out):
+    gen = features if family == "gaussian" else clip_like
+    q, keys = gen(nq, D, 1000 + D, dev), gen(nk, D, 2000 + D, dev)
+    m = search.check_coarse("bf16", k, "topk_ab")
+    idx_k, idx_q = search.EmbeddingIndex(keys, coarse="bf16"), search.EmbeddingIndex(q, coarse="bf16")
+    leg_c = lambda: (idx_k.search(q, k), idx_q.search(keys, k))
+    if a.kernels_only:
+        for _ in range(10):
+            leg_c()
+        torch.cuda.synchronize()
+        return True
+    for _ in range(2):
+        leg_batched(q, keys, k)
+        leg_device(q, keys, k)
+        leg_c()
+    ok, shares = True, []
+    for index, qq, kk in ((idx_k, q, keys), (idx_q, keys, q)):
+        v, i, info = index.search(qq, k, return_info=True)
+        ok &= equal((v, i), search.topk_embeds(qq, kk, k)) and equal((v, i), search.topk_embeds(qq, kk, k, coarse="bf16"))
+        shares.append((1.0 - info.n_fallback / qq.shape[0], qq.shape[0]))
+    per = {"A'": [], "E": [], "C": [], "C1": [], "C2": [], "P": [], "O": []}
+    for _ in range(a.rounds):
+        per["A'"].append(events(lambda: leg_batched(q, keys, k), a.iters))
+        per["E"].append(events(lambda: leg_device(q, keys, k), a.iters))
+        per["C"].append(events(leg_c, a.iters))
+        per["C1"].append(events(lambda: idx_k.search(q, k), a.iters))
+        per["C2"].append(events(lambda: idx_q.search(keys, k), a.iters))
+        per["P"].append(events(lambda: (search.summary(search.prepare(keys)[1]), search.summary(search.prepare(q)[1])), a.iters))
+        per["O"].append(events(lambda: (search.topk_embeds(q, keys, k, coarse="bf16"), search.topk_embeds(keys, q, k, coarse="bf16")), a.iters))
+    dense = per["A'"]
+    c, e, ab = (statistics.median(per[x]) for x in ("C", "E", "A'"))
+    ws = [int(search.clib().madtp_ctopk_workspace(n1, n2, D, k, m)) for n1, n2 in ((nq, nk), (nk, nq))]
+    lines = [f"{family}: nq {nq} nk {nk} D {D} k {k} m {m}: coarse and exact outputs {'EQUAL' if ok else 'DIFFER'}; certified "
+             f"{100 * shares[0][0]:.2f} % of {shares[0][1]} rows, {100 * shares[1][0]:.2f} % of {shares[1][1]} rows",
+             f"  leg E  exact route, both directions               {summary(per['E'])}",
+             f"  leg A' dense + one batched topk per direction     {summary(dense)}",
+             f"  leg C  coarse route over a prepared gallery       {summary(per['C'])}   E / C = {e / c:.2f}x{'' if e > c else '   COARSE LOSES'}"
+             f"   A' / C = {ab / c:.2f}x{'' if ab > c else '   COARSE LOSES'}",
+             f"      {nq} x {nk}: {summary(per['C1'])}   {nk} x {nq}: {summary(per['C2'])}",
+             f"  gallery prepare + summary, both galleries         {summary(per['P'])}",
+             f"  one-shot topk_embeds(coarse='bf16'), both (= C + P) {summary(per['O'])}",
+             f"  re-scoring gathers {nq} x {m} + {nk} x {m} rows of {4 * D} B = {(nq + nk) * m * 4 * D / 1e6:.1f} MB; workspaces "
+             f"{ws[0] / 1e6:.1f} + {ws[1] / 1e6:.1f} MB"]
+    for line in lines:
+        print(line, flush=True)
+        out.append(line)
+    return ok
+
+
+def coarse_main(a):
+    out = [f"tools/topk_ab.py --coarse on {torch.cuda.get_device_name(0)}: {a.rounds} alternating rounds, {a.iters} calls per leg and round, "
+           "device events, medians of per-round medians"]
+    cases = [(a.nq, a.nk, a.dim, a.k)] if a.nq and a.nk else COARSE_CASES
+    ok = True
+    for nq, nk, D, k in cases:
+        for family in ("gaussian", "clip_like")[:1 if a.kernels_only else 2]:
+            ok &= coarse_case(nq, nk, D, k, family, a, "cuda", out)
+    if a.kernels_only:
+        return
+    out.append("kernels of search_coarse.hip (tools/kernel_resources.py): VGPRs, AGPRs, LDS bytes per workgroup, waves per SIMD")
+    out += [f"  {name}: {v} VGPRs, {g} AGPRs, {lds} B, {w}" for name, v, g, lds, w in COARSE_KERNELS]
+    path = a.out if a.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "topk_coarse_ab.txt")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as fh:
+        fh.write("\n".join(out) + "\n")
+    if not ok:
+        raise SystemExit("topk_ab: the coarse and the exact route returned different outputs")
+
+
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "topk_ab.txt")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--coarse", action="store_true", help="the certified bf16 shortlist against the exact and the dense route")
+    ap.add_argument("--kernels-only", action="store_true", help="with --coarse: ten coarse searches per shape, for a kernel trace")
     ap.add_argument("--nq", type=int, default=0)
     ap.add_argument("--nk", type=int, default=0)
     ap.add_argument("--dim", type=int, default=256)
@@ -149,11 +257,13 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--no-loop", action="store_true", help="skip leg A (nq + nk launches per round)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "topk_ab.txt"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("topk_ab: needs the GPU (a CPU run measures nothing)")
     hip.load()
+    if a.coarse:
+        return coarse_main(a)
     cases = [(a.nq, a.nk, a.dim, a.k)] if a.nq and a.nk else [(5000, 25010, 256, 256), (5000, 25010, 512, 10), (5000, 25010, 768, 10),
                                                                (1000, 5000, 256, 128)]
     out = [f"tools/topk_ab.py on {torch.cuda.get_device_name(0)}: {a.rounds} alternating rounds, leg A once and the others {a.iters} calls "
