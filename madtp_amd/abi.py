@@ -9,7 +9,7 @@ uint32_t and uint64_t are the ctypes type of the same name (`unsigned long long`
 This is not a C parser: it takes what this header uses and refuses (ValueError naming the text) anything else - an unknown type, a
 declarator it cannot split, a `madtp_*(` without a signature - because a guessed argument type fails on the GPU, not at import.
 
-The side headers next to it (madtp_image.h, madtp_augment.h, madtp_jpeg.h, madtp_jhuff.h, madtp_search.h, madtp_csearch.h) are read the same way by
+The side headers next to it (madtp_image.h, madtp_augment.h, madtp_jpeg.h, madtp_jhuff.h, madtp_search.h, madtp_csearch.h, madtp_lists.h) are read the same way by
 bind(), which also returns the lib() that sets their signatures on the loaded library and checks their own version number."""
 import ctypes
 import os

@@ -411,9 +411,39 @@ def all_gather_scores(score_i2t, score_t2i):
     return outs[0], outs[1]
 
 
+def all_gather_lists(lists_i2t, lists_t2i):
+    """all_gather_scores() for what evaluate(scores="lists") returns: every rank contributes the rows it re-ranked (rank_rows) of
+    idx and val, padded to the common step, and all ranks end up with the lists of a single-rank evaluation, on the device the
+    lists are on (through the host with a gloo group).  16 bytes per slot: n * k_test pairs instead of two n_img x n_txt
+    matrices.  No-op without a process group."""
+    import torch.distributed as dist
+    from .lists import CandidateLists
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return lists_i2t, lists_t2i
+    world, rank = dist.get_world_size(), dist.get_rank()
+    outs = []
+    for cl in (lists_i2t, lists_t2i):
+        dev = cl.idx.device if dist.get_backend() == "nccl" else torch.device("cpu")
+        (n, k), step = cl.idx.shape, cl.idx.shape[0] // world + 1
+        s, e = rank_rows(n, rank, world)
+        whole = []
+        for t, empty in ((cl.idx, -1), (cl.val, cl.fill)):
+            mine = torch.full((step, k), empty, dtype=t.dtype, device=dev)
+            mine[:e - s] = t[s:e]
+            parts = [torch.empty_like(mine) for _ in range(world)]
+            dist.all_gather(parts, mine)
+            full = torch.full((n, k), empty, dtype=t.dtype, device=dev)
+            for r, part in enumerate(parts):
+                rs, re = rank_rows(n, r, world)
+                full[rs:re] = part[:re - rs]
+            whole.append(full.to(cl.idx.device))
+        outs.append(CandidateLists(whole[0], whole[1], cl.nk, cl.fill))
+    return outs[0], outs[1]
+
+
 @torch.no_grad()
 def evaluate(model, data_loader, device, config, temperature=0, rank=0, world_size=1, text_bs=256, kv_cache=True,
-             candidates="dense", coarse=None):
+             candidates="dense", coarse=None, scores="dense"):
     """compress_retrieval_dtp.py evaluate() :84-207 -> (score_matrix_i2t, score_matrix_t2i) as numpy arrays and the GFLOPs
     placeholder (0.0: the reference's fvcore count of the TRAINING forward is out of scope, harness.nlvr_forward_flops is
     the analytic counter of this repo).  rank / world_size select this process's row slices exactly as :158-162 / :181-183
@@ -425,9 +455,17 @@ def evaluate(model, data_loader, device, config, temperature=0, rank=0, world_si
     loops and never forms sims_matrix (its ITC term is the exact-f32 score of that kernel, its order among equal scores the one
     of madtp_search.h).
     coarse: None, or "bf16" with candidates="device": the same candidates through the certified bf16 shortlist of
-    search.topk_embeds (k_test <= 128)."""
+    search.topk_embeds (k_test <= 128).
+    scores: "dense" (the default) returns the two matrices; "lists" with candidates="device" returns (lists.CandidateLists image ->
+    text, the same text -> image, 0.0) on the device instead: the k_test re-ranked values of a row next to the indices topk_embeds
+    gave it, rows outside this rank's slice empty - the matrices are .to_dense() of them and are never allocated.  Several ranks
+    exchange them with all_gather_lists(); retrieval_eval.itm_eval() takes them as they are."""
     if candidates not in ("dense", "device"):
         raise ValueError(f"candidates = {candidates!r}: expected 'dense' or 'device'")
+    if scores not in ("dense", "lists"):
+        raise ValueError(f"scores = {scores!r}: expected 'dense' or 'lists'")
+    if scores == "lists" and candidates != "device":
+        raise ValueError(f"scores = 'lists' needs candidates='device' (candidates = {candidates!r})")
     k_test = config['k_test']
     if coarse is not None:
         from . import search
@@ -485,6 +523,23 @@ def evaluate(model, data_loader, device, config, temperature=0, rank=0, world_si
         sims_matrix = image_embeds @ text_embeds.t()  # :155
         sims_t = sims_matrix.t()
         top_i2t, top_t2i = (lambda i: sims_matrix[i].topk(k=k_test, dim=0)), (lambda i: sims_t[i].topk(k=k_test, dim=0))
+    if scores == "lists":
+        from .lists import CandidateLists
+
+        def reranked(n_rows, nk, sim, idx, pairs):
+            """the loops below with row i's k_test values written next to its indices instead of scattered into a dense row;
+            the rows of other ranks stay empty (the dense route leaves them at -100)"""
+            start, end = rank_rows(n_rows, rank, world_size)
+            val = torch.full((n_rows, k_test), -100.0, device=device)
+            for i in range(start, end):
+                val[i] = rerank(*pairs(i, idx[i])) + sim[i]
+            held = torch.full_like(idx, -1)
+            held[start:end] = idx[start:end]
+            return CandidateLists(held, val, nk)
+        return (reranked(n_img, num_text, i2t_sim, i2t_idx, lambda i, top: (
+                    text_ids[top], text_atts[top], torch.full((k_test,), i, dtype=torch.long, device=device))),
+                reranked(num_text, n_img, t2i_sim, t2i_idx, lambda i, top: (
+                    text_ids[i].repeat(k_test, 1), text_atts[i].repeat(k_test, 1), top)), 0.0)
     score_i2t = torch.full((n_img, num_text), -100.0, device=device)
     start, end = rank_rows(n_img, rank, world_size)
     for i in range(start, end):  # :164-174

@@ -74,9 +74,7 @@ __global__ __launch_bounds__(RK_THREADS) void rank_target_scores_kernel(RankArgs
 
 // ---- pass 2: the counts.  Workgroup (row tile, split) walks its key tiles; every accumulator is compared with the targets of
 // its row and each lane keeps integer counts, summed over the lanes and waves at the end (integers: any order is exact).
-__device__ __forceinline__ int rank_beats(float s, int col, float st, int tc) {
-    return ((s > st) & (col != tc)) | ((s == st) & (col > tc));
-}
+// (rank_beats, the comparison, is in eval_device.h: lists.hip counts with it too)
 
 __global__ __launch_bounds__(RK_THREADS) void rank_count_kernel(RankArgs a) {
     __shared__ __attribute__((aligned(16))) float Qs[RK_RT][RK_LD];

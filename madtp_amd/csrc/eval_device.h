@@ -29,6 +29,13 @@ struct RankArgs {
     const int32_t* row_count = nullptr;
 };
 
+// The one comparison of the rank rule, rank(t) = #{j != t : s_j > s_t} + #{j > t : s_j == s_t}: does key `col` with score s stand
+// before target tc with score st?  IEEE comparisons: a NaN on either side beats nothing, -0 ties with +0.  Shared by eval.hip
+// (dense rows and embeddings) and lists.hip (candidate lists).
+__device__ __forceinline__ int rank_beats(float s, int col, float st, int tc) {
+    return ((s > st) & (col != tc)) | ((s == st) & (col > tc));
+}
+
 // The one product routine of the retrieval kernels: acc0 / acc1 = rows [r0, r0 + 16) / [r0 + 16, r0 + 32) of q against the 64 key
 // rows krow[] that the caller names (thread t stages feature quad 4 (t % 16) of the tile's columns t / 16 + 16 i; -1 = a column of
 // zeros).  Lane (c, g) = (l & 15, l >> 4) of wave w holds [row 4 g + i][column 16 w + c] in register i.  Every element is the

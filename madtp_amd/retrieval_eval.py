@@ -93,7 +93,18 @@ def recall_metrics(ranks_i2t, ranks_t2i):
 def itm_eval(scores_i2t, scores_t2i, txt2img, img2txt):
     """The drivers' itm_eval(scores_i2t, scores_t2i, txt2img, img2txt) -> the nine-key dict.  Device tensors are ranked where
     they are (a view whose rows are not contiguous, such as sims.t(), from a row-major copy); numpy arrays (what
-    blip_retrieval.evaluate() returns) are uploaded first."""
+    blip_retrieval.evaluate() returns) are uploaded first.  Two lists.CandidateLists (evaluate(scores="lists")) are ranked as
+    lists (madtp_lists_rank): the same ranks, and no matrix is formed."""
+    from .lists import CandidateLists
+    if isinstance(scores_i2t, CandidateLists) or isinstance(scores_t2i, CandidateLists):
+        if not (isinstance(scores_i2t, CandidateLists) and isinstance(scores_t2i, CandidateLists)):
+            raise ValueError("itm_eval: one argument is a CandidateLists, the other is not")
+        n_img, n_txt = scores_i2t.shape[0], scores_t2i.shape[0]
+        if (scores_i2t.nk, scores_t2i.nk) != (n_txt, n_img):
+            raise ValueError(f"the lists are over {scores_i2t.nk} texts and {scores_t2i.nk} images, expected {n_txt} and {n_img}")
+        t = target_lists(txt2img, img2txt, n_img, n_txt, device=scores_i2t.device)
+        return recall_metrics(scores_i2t.rank(t.i2t_ptr, t.i2t_idx)[0], scores_t2i.rank(t.t2i_ptr, t.t2i_idx)[0])
+
     def dev(m):
         if not torch.is_tensor(m):
             m = torch.from_numpy(np.ascontiguousarray(m, dtype=np.float32)).cuda()
