@@ -59,7 +59,7 @@ const char* madtp_strerror(int code);
  * f16-split operands above: three f16 MFMA products per logical product, fp32-accurate; acc_scale = the weight's 2^-s).
  * W must be padded by the caller to a multiple of 128 rows (zero rows) - n_pad rows are read, N columns stored.
  * bias (f32, may be NULL), residual (f32 [M,ldr], may be NULL), C dtype c_dtype with leading dimension ldc
- * (BF16 output needs BF16 operands, F16S output F16S operands; F32 output is always available).
+ * (BF16 output needs BF16 or F32 operands, F16 output F16 operands, F16S output F16S operands; F32 output is always available).
  * K must be a multiple of 64 (bf16, f16-split) / 32 (f32); lda, ldw in elements (f16 elements for F16S: both >= 2K). */
 int madtp_gemm(const void* A, const void* W, const float* bias, const float* residual, void* C,
                int M, int N, int K, int lda, int ldw, int ldc, int ldr,

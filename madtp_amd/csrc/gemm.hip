@@ -1201,6 +1201,10 @@ static int gemm_launch(const void* A, const void* W, const float* bias, const fl
     }
     if (pl.status) return pl.status;
     g.ntm = pl.ntm; g.ntn = pl.ntn; g.ngrp = pl.ngrp; g.desc = pl.desc; g.fast_epi = pl.fast_epi;
+    // The vector epilogue adds a residual to f32 outputs only (every kernel instantiates its HAS_RES form for OM_F32 alone), and the
+    // plan keeps 2-byte outputs away from it but not the split one: an f16-split output with a residual came out WITHOUT the residual
+    // whenever N and ldc were multiples of 8.  No caller on the path asks for it; it takes the scalar epilogue, which adds it.
+    if (residual && c_dtype == MADTP_F16S) g.fast_epi = 0;
     g.sk = pl.sk; g.sk_ws = skw.ws; g.sk_tick = skw.tick;
     g.range_flag = (c_dtype == MADTP_F16S || c_dtype == MADTP_F16) ? madtp_internal_range_flag() : nullptr;
 

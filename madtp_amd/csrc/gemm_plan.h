@@ -149,7 +149,8 @@ inline GemmPlan gemm_plan(const GemmProblem& p, const GemmSwitches& sw, const St
     }
     // vector epilogue needs 16-byte aligned rows on every epilogue operand
     // (and, for the descriptor-bounded stores, a 256-row block of C below 2 GiB; bf16 output with an f32 residual has no
-    // caller on the path and takes the scalar epilogue)
+    // caller on the path and takes the scalar epilogue; so does an f16-split output with a residual, but gemm_launch sees to
+    // that one: this rule is pinned as recorded, tests/test_gemm_plan_cpu.py)
     r.fast_epi = (N % 8 == 0) && (p.ldc % 8 == 0) && p.c_aligned && (!p.bias || p.bias_aligned) &&
                  (!p.residual || (p.res_aligned && p.ldr % 4 == 0 && c_dtype != MADTP_BF16 && c_dtype != MADTP_F16)) &&
                  (size_t)p.ldc * 256 * 4 < ((size_t)1 << 31);

@@ -1002,15 +1002,27 @@ def profile_end():
     return rows
 
 
-def gemm_splitk_ln(a, w, bias, residual, gamma, beta, eps, splits, n, scale=1.0, want_bf16=False, lp=None):
-    """LayerNorm(scale*(a @ w^T + bias) + residual) via split-K partials; returns (y32, low-precision copy or None)."""
+def gemm_splitk(a, w, splits, n, part=None):
+    """madtp_gemm_splitk: part[s] = a[:, Ks] @ w[:, Ks]^T for K range s of `splits`, raw f32 accumulators (a prepared weight's
+    accumulator scale w_scale_of(w) is NOT applied: madtp_splitk_ln does that).  part: a contiguous f32 [splits, M, n] to fill."""
     M, K = a.shape
     if a.dtype == torch.float16:
         K //= 2
-    lp = lp or (torch.bfloat16 if want_bf16 else None)
-    part = torch.empty((splits, M, n), device=a.device, dtype=torch.float32)
+    if part is None:
+        part = torch.empty((splits, M, n), device=a.device, dtype=torch.float32)
+    elif tuple(part.shape) != (splits, M, n):
+        raise RuntimeError(f"gemm_splitk: part {tuple(part.shape)} is not {(splits, M, n)}")
+    _req(part, torch.float32, "part")
     _check(load().madtp_gemm_splitk(_p(a), _p(w), _p(part), M, n, K, a.stride(0), w.stride(0), splits, _dt(a), _stream()),
            "madtp_gemm_splitk")
+    return part
+
+
+def gemm_splitk_ln(a, w, bias, residual, gamma, beta, eps, splits, n, scale=1.0, want_bf16=False, lp=None):
+    """LayerNorm(scale*(a @ w^T + bias) + residual) via split-K partials; returns (y32, low-precision copy or None)."""
+    M = a.shape[0]
+    lp = lp or (torch.bfloat16 if want_bf16 else None)
+    part = gemm_splitk(a, w, splits, n)
     y32 = torch.empty((M, n), device=a.device, dtype=torch.float32)
     ylp = _lp_empty((M, n), a.device, lp) if lp is not None else None
     _check(load().madtp_splitk_ln(_p(part), splits, _p(bias), _p(residual), _p(gamma), _p(beta), _p(y32), _p(ylp),

@@ -38,6 +38,7 @@ def _pad128(w):
                                    (257, 2, 768)])
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_gemm(hip, M, N, K, dtype):
+    """(every small-tile variant x operand format x output mode, both epilogues, walked tiles: tests/test_gemm_small_gpu.py)"""
     a = _rand(M, K, seed=1)
     w = _rand(N, K, seed=2, scale=0.05)
     bias = _rand(N, seed=3)
