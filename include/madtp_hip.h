@@ -109,7 +109,11 @@ int madtp_gemm_plan(int M, int N, int K, int lda, int ldw, int ldc, int ldr, int
  *           (fewer operand re-reads: less CU time per launch);
  *       sq_cost <= 0 / small_tile -2 = the process default (MADTP_GEMM_SQ_COST, else 1.7 / MADTP_GEMM_SMALL_CFG, else -1) -
  *           concurrent callers with different needs do not share state.
- *       Results never depend on these attributes (same arithmetic per output element in every kernel choice).
+ *       A kernel gives the same bits on any grid, and on bf16, f16 and f32 operands results never depend on these attributes (same
+ *       arithmetic per output element in every kernel choice).  On f16-split operands the ping-pong kernel adds the three products
+ *       of a k-slab as three slabs of its stream and differs from the other kernels in low-order bits (within 3e-7 of |A||W|^T,
+ *       tests/test_gemm_big_gpu.py): where the attributes move the automatic choice between it and the wave-specialised kernel
+ *       (M >= 4096), they show in those bits.
  *   madtp_stream_destroy        forgets the attributes and destroys a stream made by madtp_stream_create_cumask.
  * Attributes may be set for any stream (also one the caller created); up to 64 streams per process carry attributes. */
 int madtp_stream_create_cumask(void** stream_out, const uint32_t* mask, int words);
