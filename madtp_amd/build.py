@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmadtp_hip.so")
-SOURCES = ["gemm.hip", "gemm_pp.hip", "attention.hip", "norm.hip", "prune.hip", "layers.hip", "lmhead.hip", "backward.hip", "retrieval.hip", "clip.hip", "eval.hip", "optim.hip", "image.hip", "augment.hip", "jpeg.hip", "search.hip", "jpeg_huff.hip", "search_coarse.hip", "lists.hip", "png.hip", "tokenmap.hip"]
+SOURCES = ["gemm.hip", "gemm_pp.hip", "attention.hip", "norm.hip", "prune.hip", "layers.hip", "lmhead.hip", "backward.hip", "retrieval.hip", "clip.hip", "eval.hip", "optim.hip", "image.hip", "augment.hip", "jpeg.hip", "search.hip", "jpeg_huff.hip", "search_coarse.hip", "lists.hip", "png.hip", "tokenmap.hip", "text.hip"]
 INCLUDE = os.path.join("..", "..", "include")
 # what is on disk, as paths from csrc/: a header nobody listed cannot leave a stale library
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + \

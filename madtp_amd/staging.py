@@ -1,6 +1,7 @@
-"""What the image input path shares on the host: the pinned staging ring behind every batch's one host-to-device copy
+"""What the input paths share on the host: the pinned staging ring behind every batch's one host-to-device copy
 (preprocess.ImagePipeline, jpeg.JpegDecoder, jpeg_device.DeviceJpegDecoder), align(), and the bounded thread pool of the decoders."""
 import concurrent.futures
+import threading
 
 import torch
 
@@ -64,3 +65,29 @@ class Pool:
         futures = [self._pool.submit(fn, j) for j in jobs]
         concurrent.futures.wait(futures)  # all of them: a failed batch leaves no thread writing into the staging buffer
         return [f.result() for f in futures]
+
+
+class StatusWaiter:
+    """The wait for a launch's status words: copied on a side stream, behind an event recorded after the kernel, into a pinned
+    buffer; only that stream is synchronised."""
+
+    def __init__(self):
+        self._lock = threading.Lock()
+        self._side, self._host = {}, None
+
+    def read(self, status):
+        dev, n = status.device, status.numel()
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev))
+        with self._lock:
+            side = self._side.get(dev)
+            if side is None:
+                side = self._side[dev] = torch.cuda.Stream(device=dev)
+            if self._host is None or self._host.numel() < n:
+                self._host = torch.empty(max(n, 256), dtype=torch.int32, pin_memory=True)
+            side.wait_event(done)
+            status.record_stream(side)
+            with torch.cuda.stream(side):
+                self._host[:n].copy_(status, non_blocking=True)
+            side.synchronize()
+            return self._host[:n].numpy().copy()

@@ -15,12 +15,11 @@ still owned a slot alone) describe the whole run.  Device tensors only: a CPU te
 functions run the kernels' lane routines on the host for checking without a GPU)."""
 import collections
 import os
-import threading
 
 import numpy as np
 import torch
 
-from . import abi, hip
+from . import abi, hip, staging
 
 HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "madtp_tokenmap.h")
 # the one declaration of the madtp_tokenmap_* entry points, next to the sources (abi.bind takes an absolute path as it is); lib() is
@@ -131,30 +130,7 @@ def _gpu_ok(t, dt):
     return None
 
 
-class _Waiter:
-    """The wait for a launch's status words: copied on a side stream, behind an event recorded after the kernel, into a pinned
-    buffer; only that stream is synchronised."""
-
-    def __init__(self):
-        self._lock = threading.Lock()
-        self._side, self._host = {}, None
-
-    def read(self, status):
-        dev, n = status.device, status.numel()
-        done = torch.cuda.Event()
-        done.record(torch.cuda.current_stream(dev))
-        with self._lock:
-            side = self._side.get(dev)
-            if side is None:
-                side = self._side[dev] = torch.cuda.Stream(device=dev)
-            if self._host is None or self._host.numel() < n:
-                self._host = torch.empty(max(n, 256), dtype=torch.int32, pin_memory=True)
-            side.wait_event(done)
-            status.record_stream(side)
-            with torch.cuda.stream(side):
-                self._host[:n].copy_(status, non_blocking=True)
-            side.synchronize()
-            return self._host[:n].numpy().copy()
+_Waiter = staging.StatusWaiter  # (the wait for a launch's status words, shared with text.py)
 
 
 _waiter = _Waiter()
